@@ -16,12 +16,18 @@ collective of the path -- the all-gather of the per-island log-evidences over RC
 (smc_comm_*), once per RUN of T steps -- is timed on its own and reported beside the
 value (`evidence_gather_ms`).  Inputs are resident in HBM before the timed region starts.
 
-The timed region of exactly K steps (barrier + device sync on both sides) is repeated R times
-on consecutive stretches of the same run (R such that about 10^4 steps are timed in all);
-`ms_per_step` / `value` are the MEDIAN repetition, the spread is reported beside them -- a
-K = 20 region lasts half a millisecond and a single shot of it is noise.
+The timed region is exactly K = --steps steps (barrier + device sync on both sides).  --reps R
+repeats it on consecutive stretches of the same run (R = 0, the default under --full: R such that
+about 10^4 steps are timed in all; a plain run times the K steps once); `ms_per_step` / `value` are
+then the MEDIAN repetition, the spread is reported beside them -- a K = 20 region lasts half a
+millisecond and a single shot of it is noise.
 
-Rank 0 prints ONE JSON line (see README / task contract), including
+A plain run sets up, warms up, times the K steps, writes --dump-outputs DIR if asked, and prints
+ONE JSON line (see README / task contract) with the headline.  --dump-outputs DIR writes what the
+timed path computed in its last step -- the particles X, the log-weights lw, the normalised weights
+W, the ancestors A (as float64) and every island's log-evidence logLt -- as DIR/<name>.npy (a fixed,
+seeded sample of rows when the whole would pass 64 MB, with its row numbers in DIR/rows.npy).
+Everything else moves behind --full, whose line also carries
   roofline        -- the longer of the step's two kernels (resampling: k_ancestors2 /
                      k_ancestors; propagate: k_propagate): algorithmic bytes per launch over
                      its average duration, BOTH measured with HIP events on the filter's stream
@@ -34,7 +40,10 @@ Rank 0 prints ONE JSON line (see README / task contract), including
                      (oracle/), with the reference's figures from profiles/cpu_reference.json beside it;
   other_workloads -- N=1, default workload only: one bounded measurement of each of the other
                      BASELINE.json configs (C3 x three schemes, C4, C4 collapsed weight, C5) with
-                     value, ms_per_step, step_frac and the dominant kernel's roofline fraction.
+                     value, ms_per_step, step_frac and the dominant kernel's roofline fraction;
+  self_check      -- c2: the run's evidence estimate beside the exact Kalman value;
+  multiSMC        -- c5: one call of multiSMC timed with everything it does;
+  N > 1           -- evidence_gather_ms and ms_per_step_with_gather (the path's one collective timed).
 
 A single BASELINE.json config as the headline of the line: --workload c3 (StochVol N=2^22; --scheme),
 c4 (d=32 guided), c5 (32 islands x 2^18 per GPU; `--workload c5 --gpus 8` is the 256-island run).
@@ -201,12 +210,14 @@ def reference_available():
     return os.path.isdir(os.path.join(REFERENCE_DIR, "particles"))
 
 
-def _cpu_worker(kind, N, nsteps, nruns, gate, Tdata=0, index=0):
+def _cpu_worker(kind, N, nsteps, nruns, gate, Tdata=0, index=0, data=""):
     """One worker PROCESS of the CPU baseline (bench.py --cpu-worker ...): `nruns` independent
     bootstrap filters of N particles over the first `nsteps` observations, one after the other,
     on one core; run r of worker `index` is seeded 123 + index * nruns + r -- distinct seeds over the whole
     pool, as multiSMC's workers get them (utils.py:189-213).  gate: a directory -- the worker drops a `ready.<pid>` file when its imports are
     done and starts when the parent creates `go` (so that all workers run at the same time).
+    data (kind "port"): a .npy file of the observations, written by the parent -- synthetic_data simulates on the
+    device, and a worker of a CPU leg must not open the GPU.
     Prints {"t0", "t1", "seconds", "logLt"}; the parent aggregates."""
     for k in ("OMP_NUM_THREADS", "OPENBLAS_NUM_THREADS", "MKL_NUM_THREADS"):
         os.environ[k] = "1"
@@ -226,7 +237,8 @@ def _cpu_worker(kind, N, nsteps, nruns, gate, Tdata=0, index=0):
             return pf.cpu_time, float(pf.logLt)       # the reference's own timer (utils.py:81-89)
     else:
         from oracle import smc_oracle as orc
-        y = synthetic_data(max(nsteps, Tdata))        # (the GPU run's series, of which the first nsteps are filtered)
+        # (the GPU run's series, of which the first nsteps are filtered)
+        y = list(np.load(data)) if data else synthetic_data(max(nsteps, Tdata))
 
         def one(seed):
             np.random.seed(seed)
@@ -248,12 +260,18 @@ def _cpu_worker(kind, N, nsteps, nruns, gate, Tdata=0, index=0):
 
 
 def _spawn_workers(kind, N, nsteps, runs_per_worker, nworkers, Tdata=0):
+    import shutil
     import tempfile
-    gate = tempfile.mkdtemp(prefix="smc_cpu_gate_") if nworkers > 1 else ""
+    tmp = tempfile.mkdtemp(prefix="smc_cpu_gate_")
+    gate = tmp if nworkers > 1 else ""
+    data = ""
+    if kind == "port":
+        data = os.path.join(tmp, "y.npy")
+        np.save(data, np.asarray(synthetic_data(max(nsteps, Tdata)), dtype=np.float64))
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--cpu-worker", kind, str(N), str(nsteps),
            str(runs_per_worker), gate, str(int(Tdata))]
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
-    procs = [subprocess.Popen(cmd + [str(i)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=ROOT, env=env)
+    procs = [subprocess.Popen(cmd + [str(i), data], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=ROOT, env=env)
              for i in range(nworkers)]
     if gate:
         t_wait = time.time()        # all imports done (or a worker died / 120 s passed): go
@@ -276,9 +294,7 @@ def _spawn_workers(kind, N, nsteps, runs_per_worker, nworkers, Tdata=0):
             failed.append("rc=%d %s" % (p.returncode, se[-200:].strip()))
             continue
         outs.append(json.loads(so.strip().splitlines()[-1]))
-    if gate:
-        import shutil
-        shutil.rmtree(gate, ignore_errors=True)
+    shutil.rmtree(tmp, ignore_errors=True)
     if not outs:
         raise RuntimeError("every cpu worker failed: " + "; ".join(failed[:3]))
     if failed:
@@ -330,7 +346,7 @@ def cpu_baseline(N, nsteps, all_cores=True, kind=None, Tdata=0):
         #  interpreter with numpy and scipy loaded: at most SMC_BENCH_CPU_WORKERS = 64 of them)
         Na = min(N, 1 << 18)
         Ta = max(1, min(nsteps, int(1e8 // Na) if kind == "port" else int(3e7 // Na)))
-        nw = max(1, min(nproc, int(os.environ.get("SMC_BENCH_CPU_WORKERS", "64"))))
+        nw = cpu_workers(nproc)
         per = max(1, -(-16 // nw))
         try:
             ws = _spawn_workers(kind, Na, Ta, per, nw)
@@ -349,6 +365,13 @@ def cpu_baseline(N, nsteps, all_cores=True, kind=None, Tdata=0):
         except Exception as e:          # the leg is a reported baseline: it must not cost the line
             out["all_cores"] = {"error": "%s: %s" % (type(e).__name__, e), "cores": nw, "host_nproc": nproc}
     return out
+
+
+def cpu_workers(nproc):
+    """Worker processes of the all-cores leg: one per core, at most SMC_BENCH_CPU_WORKERS (64), and no more than the
+    job's CPU allowance where the environment states one (OMP_NUM_THREADS)."""
+    cap = int(os.environ.get("OMP_NUM_THREADS") or 0)
+    return max(1, min(nproc, int(os.environ.get("SMC_BENCH_CPU_WORKERS", "64")), cap if cap > 0 else nproc))
 
 
 def _cpu_name():
@@ -724,6 +747,38 @@ def _lib_resident():
     return bool(_lib.RESIDENT[0])
 
 
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(pf, outdir, limit=DUMP_BYTES):
+    """What a caller of the timed path receives after its last step -- X, lw, W, A of every island (rows island-major)
+    and the islands' log-evidences -- as outdir/<name>.npy in float64.  When the rows would pass `limit` bytes, a fixed
+    sample of them (seed 0, sorted; the same rows of every array) is written, with its row numbers in rows.npy."""
+    from particles_amd import _lib
+    os.makedirs(outdir, exist_ok=True)
+    pf.sync()
+    N, isl, d = pf.N, pf.n_islands, getattr(pf, "_d", 1)
+    total = N * isl
+    row_bytes = 8 * (d + 4)                         # X, lw, W, A (and the row number when sampled)
+    budget = limit - 8 * isl - 4096                 # (logLt and the .npy headers)
+    rows = None
+    if total * row_bytes > budget:
+        rows = np.sort(np.random.default_rng(0).choice(total, size=budget // row_bytes, replace=False))
+    fields = (("X", _lib.FIELD_X), ("lw", _lib.FIELD_LW), ("W", _lib.FIELD_W), ("A", _lib.FIELD_A))
+    for name, field in fields:
+        parts = []
+        for i in range(isl):
+            v = np.asarray(pf._get(field, i), dtype=np.float64)
+            if rows is not None:
+                sel = rows[(rows >= i * N) & (rows < (i + 1) * N)] - i * N
+                v = v[sel]
+            parts.append(v)
+        np.save(os.path.join(outdir, name + ".npy"), np.concatenate(parts))
+    np.save(os.path.join(outdir, "logLt.npy"), np.asarray(pf.logLts_islands, dtype=np.float64))
+    if rows is not None:
+        np.save(os.path.join(outdir, "rows.npy"), rows.astype(np.float64))
+
+
 def _spawn_ranks(n):
     import socket
     with socket.socket() as sk:
@@ -745,7 +800,8 @@ def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--cpu-worker":
         kind, N, nsteps, nruns = sys.argv[2], int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5])
         return _cpu_worker(kind, N, nsteps, nruns, sys.argv[6] if len(sys.argv) > 6 else "",
-                           int(sys.argv[7]) if len(sys.argv) > 7 else 0, int(sys.argv[8]) if len(sys.argv) > 8 else 0)
+                           int(sys.argv[7]) if len(sys.argv) > 7 else 0, int(sys.argv[8]) if len(sys.argv) > 8 else 0,
+                           sys.argv[9] if len(sys.argv) > 9 else "")
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1000)
@@ -759,8 +815,14 @@ def main():
     ap.add_argument("--workload", default="c2", choices=["c2", "c3", "c4", "c5"],
                     help="BASELINE.json config: c2 = headline (default)")
     ap.add_argument("--cpu-steps", type=int, default=150)
-    ap.add_argument("--reps", type=int, default=0,
-                    help="repetitions of the K-step timed region (0: about 10^4 timed steps in all)")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="repetitions of the K-step timed region (0: about 10^4 timed steps in all; default: 1, "
+                         "exactly --steps timed steps -- with --full, 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: roofline and launch floor, other_workloads, cpu_baseline, "
+                         "self_check, the multiSMC block (c5) and the timed evidence gather (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--no-other-workloads", action="store_true",
@@ -835,8 +897,10 @@ def main():
             sys.exit("bench.py: ranks share a GPU (%s): launch one rank per GPU" % devices)
     K, W = a.steps, a.warmup
     heavy = a.workload in ("c3", "c4", "c5")        # 0.07-0.3 ms per step: fewer timed steps do
-    R = a.reps if a.reps > 0 else max(3, min(500, -(-(2000 if heavy else 10000) // K)))
-    T = W + R * K + (K if world > 1 else 0)      # (N > 1: one more K-step region, timed WITH the evidence gather)
+    reps = a.reps if a.reps is not None else (0 if a.full else 1)
+    R = reps if reps > 0 else max(3, min(500, -(-(2000 if heavy else 10000) // K)))
+    # (--full, N > 1: one more K-step region, timed WITH the evidence gather)
+    T = W + R * K + (K if world > 1 and a.full else 0)
     wl = make_workload(a.workload, T, scheme=a.scheme, log2N=a.log2N, N=a.N, islands=a.islands,
                        essrmin=a.essrmin, collapsed=a.collapsed, qmc=a.qmc, strict=a.strict, dense=a.dense)
     a.log2N, a.islands = wl["log2N"], wl["islands"]
@@ -850,13 +914,18 @@ def main():
     # finished, without the latency of the host-side barrier itself (a TCP star: ~0.1 ms, which at
     # K = 20 steps of 20 us would be a quarter of the region).
     dts = time_steps(pf, K, W, R, grp)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(pf, a.dump_outputs)
     local_ll = pf.logLts_islands
     # the path's one collective: the all-gather of the per-island evidences, ONCE PER RUN (after the
     # T steps of a filter, not after every K-step repetition) -- timed on its own and reported
     gather_ms = None
     with_gather = None
     all_ll = local_ll
-    if grp:
+    if grp and not a.full:
+        all_ll = grp.gather_evidence(local_ll)
+        dts = grp.allreduce_max_host(dts)                  # per repetition: the slowest rank
+    elif grp:
         g = np.zeros(5)
         for i in range(5):
             grp.barrier()
@@ -881,7 +950,7 @@ def main():
     # (another random stream, the same n when --cpu-steps allows) lands in the same block below
     n_chk = int(min(a.cpu_steps, T) if a.log2N >= 18 else min(T, 2000))        # (= the CPU baseline's sample)
     self_check = None
-    if a.workload == "c2" and d == 1 and not a.qmc:
+    if a.full and a.workload == "c2" and d == 1 and not a.qmc:
         kal = kalman_loglik_toy(wl["fk"].data[:n_chk])
         self_check = {"steps": n_chk, "gpu_logLt": float(summ0[n_chk - 1, 3]), "kalman_logLt": kal,
                       "gpu_minus_kalman": float(summ0[n_chk - 1, 3]) - kal,
@@ -897,7 +966,7 @@ def main():
     # (filter construction, the T-loop, the gather): reported beside the headline, whose timed region
     # holds the steps only
     multi = None
-    if a.workload == "c5" and a.N == 0:
+    if a.full and a.workload == "c5" and a.N == 0:
         import particles_amd as pa
         wl5 = make_workload("c5", K, scheme=a.scheme, essrmin=a.essrmin, log2N=a.log2N, islands=a.islands)
         nruns = wl5["islands"] * world
@@ -954,7 +1023,7 @@ def main():
             out["rank_devices"] = devices
         if multi is not None:
             out["multiSMC"] = multi
-        if grp:
+        if grp and a.full:
             out["timing"]["ms_per_step_with_gather"] = 1e3 * with_gather / K
             out["timing"]["note"] = (
                 "per repetition: max over ranks of each rank's own [barrier, device sync, clock] ... K steps ... "
@@ -963,7 +1032,7 @@ def main():
                 % (gather_ms, 100.0 * gather_ms / (1e3 * dt / K * 1000.0)))
 
     # ---- dominant-kernel duration (HIP events on the filter's stream, outside the timed region)
-    if not a.no_profile:
+    if a.full and not a.no_profile:
         mv_ms, rs_ms, ns, kernels = kernel_profile(wl, K, W, rank)
         if rank == 0 and ns:
             out["roofline"] = add_profile_fractions(roofline(wl, out["step_achieved_GBs"], mv_ms, rs_ms, ns, kernels), wl)
@@ -989,12 +1058,12 @@ def main():
                                         "Infinity Cache)"})
                 except Exception as e:
                     out["roofline"]["limiter_error"] = "%s: %s" % (type(e).__name__, e)
-    if rank == 0 and world == 1 and a.workload == "c2" and a.N == 0 and not a.no_other_workloads \
+    if a.full and rank == 0 and world == 1 and a.workload == "c2" and a.N == 0 and not a.no_other_workloads \
             and (a.log2N == 20 or a.other_shrink):
         out["other_workloads"] = (other_workloads(K=3, W=2, R=2, shrink=a.other_shrink) if a.other_shrink
                                   else other_workloads())
         out["other_workloads"].update(small_and_generic_legs(shrink=a.other_shrink))
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and a.workload == "c2":
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and a.workload == "c2":
         nst = min(a.cpu_steps, T) if a.log2N >= 18 else min(T, 2000)
         try:
             out["cpu_baseline"] = cpu_baseline(N, nst, Tdata=T)

@@ -28,7 +28,7 @@ typedef struct { char internal[128]; } ncclUniqueId;
 enum { ncclSuccess = 0, ncclSystemError = 2, ncclInvalidArgument = 4, ncclInvalidUsage = 5 };
 
 typedef struct {
-    char dir[100];
+    char dir[128];
     int nranks, rank;
     unsigned long seq_coll;            /* collectives done on this communicator */
     unsigned long seq_p2p[64][2];      /* per peer: sends, receives */
@@ -83,9 +83,12 @@ const char* ncclGetErrorString(ncclResult_t r) { return r == 0 ? "no error" : g_
 ncclResult_t ncclGetUniqueId(ncclUniqueId* id)
 {
     memset(id, 0, sizeof *id);
+    /* a NEW directory per id (mkdtemp): a name cut short by a long TMPDIR must never lead two worlds into one
+     * directory, where the second finds the first one's files; a TMPDIR the id cannot hold falls back to /tmp */
     const char* base = getenv("TMPDIR");
-    snprintf(id->internal, 100, "%s/fake_rccl_%d_%ld", base && *base ? base : "/tmp", (int)getpid(), (long)time(NULL));
-    if (mkdir(id->internal, 0700) != 0 && errno != EEXIST) return fail(ncclSystemError, "mkdir %s failed (%ld %ld)", id->internal, errno, 0);
+    if (!base || !*base || snprintf(id->internal, sizeof id->internal, "%s/fake_rccl_XXXXXX", base) >= (int)sizeof id->internal)
+        snprintf(id->internal, sizeof id->internal, "/tmp/fake_rccl_XXXXXX");
+    if (!mkdtemp(id->internal)) return fail(ncclSystemError, "mkdtemp %s failed (%ld %ld)", id->internal, errno, 0);
     return ncclSuccess;
 }
 

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,11 +22,11 @@ def _emu_env():
 
 
 def test_default_line_carries_other_workloads_and_cpu_legs(tmp_path):
-    """`python bench.py` (N = 1, default workload) shrunk to emulator sizes: top-level fields are C2's,
+    """`python bench.py --full` (N = 1, default workload) shrunk to emulator sizes: top-level fields are C2's,
     `other_workloads` holds one measurement per remaining BASELINE.json config, `cpu_baseline` states
     the host's core count and has a one-core and an all-cores leg."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--log2N", "11",
-           "--reps", "2", "--other-shrink", "10", "--cpu-steps", "4"]
+           "--reps", "2", "--other-shrink", "10", "--cpu-steps", "4", "--full"]
     p = subprocess.run(cmd, env=_emu_env(), capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -74,10 +75,64 @@ def test_default_line_carries_other_workloads_and_cpu_legs(tmp_path):
     assert cb["kind"] == ("reference" if os.path.isdir("/root/reference/particles") else "port")
     if cb["host"]["nproc"] > 1:
         ac = cb["all_cores"]
-        assert ac["cores"] == min(64, cb["host"]["nproc"]) and ac["host_nproc"] == cb["host"]["nproc"]
+        cap = int(os.environ.get("OMP_NUM_THREADS") or 0) or cb["host"]["nproc"]     # (a job's stated CPU allowance)
+        assert ac["cores"] == min(64, cb["host"]["nproc"], cap) and ac["host_nproc"] == cb["host"]["nproc"]
         assert ac["runs"] >= 16 and ac["value"] > 0 and ac["kind"] == cb["kind"]
         # independent runs, as multiSMC's are (utils.py:189-213): every worker its own seeds (64 copies of one)
         assert ac["distinct_logLt"] == ac["runs"] and ac["logLt_sd"] > 0
+
+
+def test_plain_line_is_the_headline_and_dumps_its_outputs(tmp_path):
+    """`python bench.py` without --full: exactly --steps timed steps, the headline's contract keys and nothing that
+    takes runs of its own; --dump-outputs writes the last step's arrays, the same from run to run."""
+    outs = []
+    for run in range(2):
+        out = tmp_path / ("out%d" % run)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--log2N", "11",
+               "--dump-outputs", str(out)]
+        p = subprocess.run(cmd, env=_emu_env(), capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        for k in CONTRACT:
+            assert k in d, k
+        assert d["steps"] == 3 and d["timing"]["reps"] == 1 and d["ms_per_step"] > 0 and d["dtype"] == "f64"
+        for k in ("roofline", "other_workloads", "cpu_baseline", "self_check", "multiSMC"):
+            assert k not in d, k
+        outs.append({f: np.load(str(out / f)) for f in sorted(os.listdir(str(out)))})
+    assert sorted(outs[0]) == ["A.npy", "W.npy", "X.npy", "logLt.npy", "lw.npy"]
+    for f, v in outs[0].items():
+        assert v.dtype == np.float64 and np.array_equal(v, outs[1][f]), f
+        assert v.shape == ((1,) if f == "logLt.npy" else (1 << 11,)), (f, v.shape)
+    A = outs[0]["A.npy"]
+    assert np.all((A >= 0) & (A < 1 << 11)) and np.all(np.isfinite(outs[0]["X.npy"]))
+    assert abs(outs[0]["W.npy"].sum() - 1.0) < 1e-9 and np.isfinite(outs[0]["logLt.npy"][0])
+
+
+def test_dump_outputs_samples_large_outputs(tmp_path):
+    """Outputs beyond the byte limit: the same fixed sample of rows from every array, within the limit."""
+    import bench
+    wl = bench.make_workload("c5", 4, log2N=10, islands=2)
+    limit = 20000
+    written = []
+    for run in range(2):
+        pf = bench.make_filter(wl)
+        pf.step_async(3)
+        out = tmp_path / ("out%d" % run)
+        bench.dump_outputs(pf, str(out), limit=limit)
+        written.append({f: np.load(str(out / f)) for f in sorted(os.listdir(str(out)))})
+        del pf
+    w = written[0]
+    assert sorted(w) == ["A.npy", "W.npy", "X.npy", "logLt.npy", "lw.npy", "rows.npy"]
+    rows = w["rows.npy"]
+    assert 0 < len(rows) < 2 << 10 and np.all(np.diff(rows) > 0) and rows[-1] < 2 << 10
+    assert sum(os.path.getsize(str(tmp_path / "out0" / f)) for f in w) <= limit
+    for f in ("X.npy", "lw.npy", "W.npy", "A.npy"):
+        assert w[f].shape == rows.shape, f
+    assert w["logLt.npy"].shape == (2,)
+    for f, v in w.items():
+        assert np.array_equal(v, written[1][f]), f
 
 
 @pytest.mark.parametrize("kind", ["port", "reference"])

@@ -437,7 +437,7 @@ def test_bench_two_ranks_launch_line(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--steps", "3", "--warmup", "1", "--log2N", "11", "--reps", "2",
-           "--no-cpu-baseline", "--no-profile"]
+           "--no-cpu-baseline", "--no-profile", "--full"]
     # without RCCL the launch line FAILS, and says why in a JSON object (a scale line is never a host-star line
     # by accident) ...
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
@@ -488,7 +488,7 @@ def test_bench_eight_rank_c5_line_through_the_rccl_double(tmp_path, has_gpu):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "SMC_ALLOW_HOST_GATHER", "SMC_BENCH_NGPU"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--workload", "c5", "--log2N", "10", "--steps", "2",
-           "--warmup", "1", "--reps", "1", "--no-cpu-baseline", "--no-profile"]
+           "--warmup", "1", "--reps", "1", "--no-cpu-baseline", "--no-profile", "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1200, cwd=str(tmp_path))
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

@@ -5,7 +5,7 @@ TAG=${1:-ab}; VARS=${2:-"NEW PHILOX_LATE"}; ARGS=${3:-"--steps 1000 --warmup 50 
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
 for rep in 1 2 3; do for lib in $VARS; do
   if [ $lib = NEW ]; then unset SMC_HIP_LIBRARY; else export SMC_HIP_LIBRARY=$R/particles_amd/lib/abl/libsmc_$lib.so; fi
-  timeout 300 python bench.py $ARGS > $O/ab_${lib}_$rep.json 2>/dev/null
+  timeout 300 python bench.py --full $ARGS > $O/ab_${lib}_$rep.json 2>/dev/null
   python - $O/ab_${lib}_$rep.json $lib <<'PY'
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1]); r=d['roofline']

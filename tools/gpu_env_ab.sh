@@ -8,7 +8,7 @@ IFS=';' read -ra VL <<< "$VARS"
 for rep in $(seq 1 $REPS); do for v in "${VL[@]}"; do
   name=${v%%:*}; envs=""; [ "$v" != "$name" ] && envs=${v#*:}
   envcmd=$(echo $envs | tr ',' ' ' | sed 's|LIB=|SMC_HIP_LIBRARY='$R'/particles_amd/lib/abl/|')
-  env $envcmd timeout 300 python bench.py $ARGS > $O/ab_${name}_$rep.json 2>/dev/null
+  env $envcmd timeout 300 python bench.py --full $ARGS > $O/ab_${name}_$rep.json 2>/dev/null
   python - $O/ab_${name}_$rep.json $name <<'PY'
 import json,sys
 try:

@@ -33,8 +33,8 @@ for leg in $LEGS; do
   esac
   P=$O/prof_$leg
   mkdir -p $P
-  CMD="python bench.py $ARGS --steps $STEPS --warmup 20 --reps 3 --no-cpu-baseline --no-other-workloads --no-profile"
-  BENCH="python $R/bench.py $ARGS --steps $STEPS --warmup 20 --reps 3 --no-cpu-baseline --no-other-workloads --no-profile"
+  CMD="python bench.py --full $ARGS --steps $STEPS --warmup 20 --reps 3 --no-cpu-baseline --no-other-workloads --no-profile"
+  BENCH="python $R/bench.py --full $ARGS --steps $STEPS --warmup 20 --reps 3 --no-cpu-baseline --no-other-workloads --no-profile"
   timeout 150 rocprofv3 --kernel-trace --stats -d $P/trace -o trace -- $BENCH > $P/trace.log 2>&1
   IFS=';' read -ra PASSLIST <<< "$PASSES"
   for pass in "${PASSLIST[@]}"; do

@@ -14,9 +14,9 @@ pytest)
 smoke)
   (timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "rc=$?" >> $O/smoke.log); tail -3 $O/smoke.log ;;
 bench)
-  timeout 300 python bench.py --steps 1000 --warmup 50 > $O/bench_c2_k1000.json 2> $O/bench_c2_k1000.err
-  timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_c2_k20.json 2> $O/bench_c2_k20.err
-  timeout 300 python bench.py > $O/bench_c2_default.json 2> $O/bench_c2_default.err
+  timeout 300 python bench.py --full --steps 1000 --warmup 50 > $O/bench_c2_k1000.json 2> $O/bench_c2_k1000.err
+  timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_c2_k20.json 2> $O/bench_c2_k20.err
+  timeout 300 python bench.py --full > $O/bench_c2_default.json 2> $O/bench_c2_default.err
   for f in $O/bench_c2_*.json; do python - "$f" <<'PY'
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1]); r=d.get('roofline',{})
@@ -24,9 +24,9 @@ print(sys.argv[1].split('/')[-1], 'ms/step %.5f'%d['ms_per_step'], 'G/s %.2f'%(d
 PY
   done ;;
 ab)
-  SMC_ANC2_R1=1 timeout 300 python bench.py --steps 1000 --warmup 50 --no-cpu-baseline > $O/bench_c2_anc2r1.json 2>&1
-  SMC_NO_NT=1 timeout 300 python bench.py --steps 1000 --warmup 50 --no-cpu-baseline > $O/bench_c2_nont.json 2>&1
-  timeout 300 python bench.py --steps 1000 --warmup 50 --no-cpu-baseline --graph > $O/bench_c2_graph.json 2>&1
+  SMC_ANC2_R1=1 timeout 300 python bench.py --full --steps 1000 --warmup 50 --no-cpu-baseline > $O/bench_c2_anc2r1.json 2>&1
+  SMC_NO_NT=1 timeout 300 python bench.py --full --steps 1000 --warmup 50 --no-cpu-baseline > $O/bench_c2_nont.json 2>&1
+  timeout 300 python bench.py --full --steps 1000 --warmup 50 --no-cpu-baseline --graph > $O/bench_c2_graph.json 2>&1
   for f in $O/bench_c2_anc2r1.json $O/bench_c2_nont.json $O/bench_c2_graph.json; do python - "$f" <<'PY'
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1]); r=d.get('roofline',{})
@@ -34,9 +34,9 @@ print(sys.argv[1].split('/')[-1], 'ms/step %.5f'%d['ms_per_step'], 'G/s %.2f'%(d
 PY
   done ;;
 c345)
-  timeout 300 python bench.py --workload c5 --steps 200 --warmup 20 > $O/bench_c5.json 2>&1
-  for sc in systematic stratified multinomial; do timeout 300 python bench.py --workload c3 --scheme $sc --steps 200 --warmup 20 > $O/bench_c3_$sc.json 2>&1; done
-  timeout 300 python bench.py --workload c4 --steps 100 --warmup 10 > $O/bench_c4.json 2>&1
+  timeout 300 python bench.py --full --workload c5 --steps 200 --warmup 20 > $O/bench_c5.json 2>&1
+  for sc in systematic stratified multinomial; do timeout 300 python bench.py --full --workload c3 --scheme $sc --steps 200 --warmup 20 > $O/bench_c3_$sc.json 2>&1; done
+  timeout 300 python bench.py --full --workload c4 --steps 100 --warmup 10 > $O/bench_c4.json 2>&1
   for f in $O/bench_c5.json $O/bench_c3_*.json $O/bench_c4.json; do python - "$f" <<'PY'
 import json,sys
 try:
@@ -52,8 +52,8 @@ prof_r1)
 prof_c5)
   EXTRA="--workload c5" bash tools/gpu_profile.sh ${TAG}_c5 100 > $O/prof_c5.txt 2>&1; tail -30 $O/prof_c5.txt ;;
 benchN)
-  for n in 100000 1000000 10000000; do timeout 300 python bench.py --N $n --steps 400 --warmup 50 --no-cpu-baseline > $O/bench_N$n.json 2>&1; done
-  for sc in stratified multinomial; do timeout 300 python bench.py --N 1000000 --scheme $sc --essrmin 1.0 --steps 400 --warmup 50 --no-cpu-baseline > $O/bench_N1000000_$sc.json 2>&1; done
+  for n in 100000 1000000 10000000; do timeout 300 python bench.py --full --N $n --steps 400 --warmup 50 --no-cpu-baseline > $O/bench_N$n.json 2>&1; done
+  for sc in stratified multinomial; do timeout 300 python bench.py --full --N 1000000 --scheme $sc --essrmin 1.0 --steps 400 --warmup 50 --no-cpu-baseline > $O/bench_N1000000_$sc.json 2>&1; done
   for f in $O/bench_N*.json; do python - "$f" <<'PY'
 import json,sys
 try:
@@ -66,9 +66,9 @@ abold)
   # same box, the r03b-state library against the current one (C2, K = 1000 and K = 20, twice each, interleaved)
   for rep in 1 2; do for lib in R03B NEW; do
     if [ $lib = R03B ]; then export SMC_HIP_LIBRARY=$R/particles_amd/lib/abl/libsmc_R03B.so; else unset SMC_HIP_LIBRARY; fi
-    timeout 300 python bench.py --steps 1000 --warmup 50 --no-cpu-baseline > $O/ab_${lib}_k1000_$rep.json 2>&1
-    timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/ab_${lib}_k20_$rep.json 2>&1
-    timeout 300 python bench.py --workload c5 --steps 200 --warmup 20 --no-cpu-baseline > $O/ab_${lib}_c5_$rep.json 2>&1
+    timeout 300 python bench.py --full --steps 1000 --warmup 50 --no-cpu-baseline > $O/ab_${lib}_k1000_$rep.json 2>&1
+    timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/ab_${lib}_k20_$rep.json 2>&1
+    timeout 300 python bench.py --full --workload c5 --steps 200 --warmup 20 --no-cpu-baseline > $O/ab_${lib}_c5_$rep.json 2>&1
   done; done; unset SMC_HIP_LIBRARY
   for f in $O/ab_*.json; do python - "$f" <<'PY'
 import json,sys
@@ -95,10 +95,10 @@ smc2prof)
   timeout 300 python tools/smc2_profile.py > $O/smc2_profile.txt 2>&1; cat $O/smc2_profile.txt ;;
 quick)
   (timeout 900 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; echo "rc=$?" >> $O/pytest_gpu.log); tail -3 $O/pytest_gpu.log
-  timeout 300 python bench.py --steps 1000 --warmup 50 --no-cpu-baseline > $O/bench_c2_k1000.json 2>&1
-  timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_c2_k20.json 2>&1
-  timeout 300 python bench.py --workload c5 --steps 200 --warmup 20 --no-cpu-baseline > $O/bench_c5.json 2>&1
-  for sc in systematic stratified multinomial; do timeout 300 python bench.py --workload c3 --scheme $sc --steps 200 --warmup 20 --no-cpu-baseline > $O/bench_c3_$sc.json 2>&1; done
+  timeout 300 python bench.py --full --steps 1000 --warmup 50 --no-cpu-baseline > $O/bench_c2_k1000.json 2>&1
+  timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_c2_k20.json 2>&1
+  timeout 300 python bench.py --full --workload c5 --steps 200 --warmup 20 --no-cpu-baseline > $O/bench_c5.json 2>&1
+  for sc in systematic stratified multinomial; do timeout 300 python bench.py --full --workload c3 --scheme $sc --steps 200 --warmup 20 --no-cpu-baseline > $O/bench_c3_$sc.json 2>&1; done
   for f in $O/bench_c2_k1000.json $O/bench_c2_k20.json $O/bench_c5.json $O/bench_c3_*.json; do python - "$f" <<'PY'
 import json,sys
 try:
@@ -109,8 +109,8 @@ PY
   done ;;
 c3m)
   (timeout 900 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; echo "rc=$?" >> $O/pytest_gpu.log); tail -3 $O/pytest_gpu.log
-  SMC_FLAT_MULTINOMIAL=1 timeout 300 python bench.py --workload c3 --scheme multinomial --steps 200 --warmup 20 --no-cpu-baseline > $O/bench_c3_multinomial_flat.json 2>&1
-  timeout 300 python bench.py --workload c3 --scheme multinomial --steps 200 --warmup 20 --no-cpu-baseline > $O/bench_c3_multinomial.json 2>&1
+  SMC_FLAT_MULTINOMIAL=1 timeout 300 python bench.py --full --workload c3 --scheme multinomial --steps 200 --warmup 20 --no-cpu-baseline > $O/bench_c3_multinomial_flat.json 2>&1
+  timeout 300 python bench.py --full --workload c3 --scheme multinomial --steps 200 --warmup 20 --no-cpu-baseline > $O/bench_c3_multinomial.json 2>&1
   python - "$O/bench_c3_multinomial.json" <<'PY'
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1]); r=d.get('roofline',{})
@@ -120,8 +120,8 @@ print('   (flat path) ms/step %.5f'%d['ms_per_step'], 'G/s %.2f'%(d['value']/1e9
 PY
   ;;
 prof_benchN)
-  for n in 100000 1000000 10000000; do timeout 300 python bench.py --N $n --steps 400 --warmup 50 --no-cpu-baseline > $O/bench_N$n.json 2>&1; done
-  for sc in stratified multinomial; do timeout 300 python bench.py --N 1000000 --scheme $sc --essrmin 1.0 --steps 400 --warmup 50 --no-cpu-baseline > $O/bench_N1000000_$sc.json 2>&1; done
+  for n in 100000 1000000 10000000; do timeout 300 python bench.py --full --N $n --steps 400 --warmup 50 --no-cpu-baseline > $O/bench_N$n.json 2>&1; done
+  for sc in stratified multinomial; do timeout 300 python bench.py --full --N 1000000 --scheme $sc --essrmin 1.0 --steps 400 --warmup 50 --no-cpu-baseline > $O/bench_N1000000_$sc.json 2>&1; done
   for f in $O/bench_N*.json; do python - "$f" <<'PY'
 import json,sys
 try:
@@ -134,9 +134,9 @@ abold)
   # same box, the r03b-state library against the current one (C2, K = 1000 and K = 20, twice each, interleaved)
   for rep in 1 2; do for lib in R03B NEW; do
     if [ $lib = R03B ]; then export SMC_HIP_LIBRARY=$R/particles_amd/lib/abl/libsmc_R03B.so; else unset SMC_HIP_LIBRARY; fi
-    timeout 300 python bench.py --steps 1000 --warmup 50 --no-cpu-baseline > $O/ab_${lib}_k1000_$rep.json 2>&1
-    timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/ab_${lib}_k20_$rep.json 2>&1
-    timeout 300 python bench.py --workload c5 --steps 200 --warmup 20 --no-cpu-baseline > $O/ab_${lib}_c5_$rep.json 2>&1
+    timeout 300 python bench.py --full --steps 1000 --warmup 50 --no-cpu-baseline > $O/ab_${lib}_k1000_$rep.json 2>&1
+    timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/ab_${lib}_k20_$rep.json 2>&1
+    timeout 300 python bench.py --full --workload c5 --steps 200 --warmup 20 --no-cpu-baseline > $O/ab_${lib}_c5_$rep.json 2>&1
   done; done; unset SMC_HIP_LIBRARY
   for f in $O/ab_*.json; do python - "$f" <<'PY'
 import json,sys
@@ -163,10 +163,10 @@ smc2prof)
   timeout 300 python tools/smc2_profile.py > $O/smc2_profile.txt 2>&1; cat $O/smc2_profile.txt ;;
 quick)
   (timeout 900 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; echo "rc=$?" >> $O/pytest_gpu.log); tail -3 $O/pytest_gpu.log
-  timeout 300 python bench.py --steps 1000 --warmup 50 --no-cpu-baseline > $O/bench_c2_k1000.json 2>&1
-  timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_c2_k20.json 2>&1
-  timeout 300 python bench.py --workload c5 --steps 200 --warmup 20 --no-cpu-baseline > $O/bench_c5.json 2>&1
-  for sc in systematic stratified multinomial; do timeout 300 python bench.py --workload c3 --scheme $sc --steps 200 --warmup 20 --no-cpu-baseline > $O/bench_c3_$sc.json 2>&1; done
+  timeout 300 python bench.py --full --steps 1000 --warmup 50 --no-cpu-baseline > $O/bench_c2_k1000.json 2>&1
+  timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_c2_k20.json 2>&1
+  timeout 300 python bench.py --full --workload c5 --steps 200 --warmup 20 --no-cpu-baseline > $O/bench_c5.json 2>&1
+  for sc in systematic stratified multinomial; do timeout 300 python bench.py --full --workload c3 --scheme $sc --steps 200 --warmup 20 --no-cpu-baseline > $O/bench_c3_$sc.json 2>&1; done
   for f in $O/bench_c2_k1000.json $O/bench_c2_k20.json $O/bench_c5.json $O/bench_c3_*.json; do python - "$f" <<'PY'
 import json,sys
 try:
@@ -182,10 +182,10 @@ trace)
 abtk)
   for v in 0 1; do
     if [ $v = 1 ]; then export SMC_NO_TK=1; else unset SMC_NO_TK; fi
-    timeout 300 python bench.py --steps 1000 --warmup 50 --no-cpu-baseline > $O/bench_c2_notk$v.json 2>&1
-    timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_c2k20_notk$v.json 2>&1
-    timeout 300 python bench.py --workload c5 --steps 200 --warmup 20 --no-cpu-baseline > $O/bench_c5_notk$v.json 2>&1
-    timeout 300 python bench.py --workload c3 --steps 200 --warmup 20 --no-cpu-baseline > $O/bench_c3_notk$v.json 2>&1
+    timeout 300 python bench.py --full --steps 1000 --warmup 50 --no-cpu-baseline > $O/bench_c2_notk$v.json 2>&1
+    timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_c2k20_notk$v.json 2>&1
+    timeout 300 python bench.py --full --workload c5 --steps 200 --warmup 20 --no-cpu-baseline > $O/bench_c5_notk$v.json 2>&1
+    timeout 300 python bench.py --full --workload c3 --steps 200 --warmup 20 --no-cpu-baseline > $O/bench_c3_notk$v.json 2>&1
   done; unset SMC_NO_TK
   for f in $O/bench_*notk*.json; do python - "$f" <<'PY'
 import json,sys
@@ -198,7 +198,7 @@ PY
 bench2)
   # the N = 2 launch line of the driver, both ranks on this box's one GPU (functional: RCCL may refuse 2 ranks per device)
   SMC_BENCH_NGPU=1 SMC_ALLOW_HOST_GATHER=1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-      --master-addr 127.0.0.1 --master-port 29655 bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline --no-profile > $O/bench_2ranks_1gpu.json 2> $O/bench_2ranks_1gpu.err
+      --master-addr 127.0.0.1 --master-port 29655 bench.py --full --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline --no-profile > $O/bench_2ranks_1gpu.json 2> $O/bench_2ranks_1gpu.err
   python - "$O/bench_2ranks_1gpu.json" <<'PY'
 import json,sys
 try:

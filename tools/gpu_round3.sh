@@ -28,21 +28,21 @@ pytest)
 smoke)
   (timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "rc=$?" >> $O/smoke.log); tail -3 $O/smoke.log ;;
 bench)
-  SECONDS=0; timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_line.json 2> $O/bench_driver_line.err; echo "driver line wall ${SECONDS}s"
+  SECONDS=0; timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_line.json 2> $O/bench_driver_line.err; echo "driver line wall ${SECONDS}s"
   line $O/bench_driver_line.json; tail -3 $O/bench_driver_line.err
-  timeout 300 python bench.py --steps 1000 --warmup 50 --no-cpu-baseline --no-other-workloads > $O/bench_c2_k1000.json 2> $O/bench_c2_k1000.err
+  timeout 300 python bench.py --full --steps 1000 --warmup 50 --no-cpu-baseline --no-other-workloads > $O/bench_c2_k1000.json 2> $O/bench_c2_k1000.err
   line $O/bench_c2_k1000.json ;;
 abrng)
   # one box: table-free Box-Muller (rounds 1-2) | table-driven (this tree) | table-driven + Philox4x32-7
   for rep in 1 2; do for lib in BM_LEGACY NEW PHILOX_ROUNDS=7; do
     if [ $lib = NEW ]; then unset SMC_HIP_LIBRARY; else export SMC_HIP_LIBRARY=$R/particles_amd/lib/abl/libsmc_$lib.so; fi
-    timeout 300 python bench.py --steps 1000 --warmup 50 --no-cpu-baseline --no-other-workloads > $O/ab_${lib}_c2k1000_$rep.json 2>&1
-    timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-workloads > $O/ab_${lib}_c2k20_$rep.json 2>&1
-    timeout 300 python bench.py --workload c5 --steps 100 --warmup 10 > $O/ab_${lib}_c5_$rep.json 2>&1
+    timeout 300 python bench.py --full --steps 1000 --warmup 50 --no-cpu-baseline --no-other-workloads > $O/ab_${lib}_c2k1000_$rep.json 2>&1
+    timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-workloads > $O/ab_${lib}_c2k20_$rep.json 2>&1
+    timeout 300 python bench.py --full --workload c5 --steps 100 --warmup 10 > $O/ab_${lib}_c5_$rep.json 2>&1
     if [ $rep = 1 ]; then
-      timeout 300 python bench.py --workload c4 --steps 50 --warmup 10 > $O/ab_${lib}_c4_$rep.json 2>&1
-      timeout 300 python bench.py --workload c4 --collapsed --steps 50 --warmup 10 > $O/ab_${lib}_c4coll_$rep.json 2>&1
-      timeout 300 python bench.py --workload c3 --steps 100 --warmup 10 > $O/ab_${lib}_c3_$rep.json 2>&1
+      timeout 300 python bench.py --full --workload c4 --steps 50 --warmup 10 > $O/ab_${lib}_c4_$rep.json 2>&1
+      timeout 300 python bench.py --full --workload c4 --collapsed --steps 50 --warmup 10 > $O/ab_${lib}_c4coll_$rep.json 2>&1
+      timeout 300 python bench.py --full --workload c3 --steps 100 --warmup 10 > $O/ab_${lib}_c3_$rep.json 2>&1
     fi
   done; done; unset SMC_HIP_LIBRARY
   for f in $O/ab_*.json; do line $f; done ;;
@@ -61,7 +61,7 @@ prof_c3m)
   EXTRA="--workload c3 --scheme multinomial" bash tools/gpu_profile.sh ${TAG}_c3m 100 > $O/prof_c3m.txt 2>&1; tail -40 $O/prof_c3m.txt ;;
 c3m)
   for sc in multinomial stratified systematic; do
-    timeout 300 python bench.py --workload c3 --scheme $sc --steps 100 --warmup 10 > $O/bench_c3_$sc.json 2>&1; line $O/bench_c3_$sc.json; done ;;
+    timeout 300 python bench.py --full --workload c3 --scheme $sc --steps 100 --warmup 10 > $O/bench_c3_$sc.json 2>&1; line $O/bench_c3_$sc.json; done ;;
 robust)
   (timeout 300 python tools/robustness.py > $O/robustness.txt 2>&1; echo "rc=$?" >> $O/robustness.txt); tail -25 $O/robustness.txt
   (timeout 300 python tools/soak.py > $O/soak.txt 2>&1; echo "rc=$?" >> $O/soak.txt); tail -8 $O/soak.txt
@@ -78,14 +78,14 @@ prof_c5)
 prof_c4)
   EXTRA="--workload c4" bash tools/gpu_profile.sh ${TAG}_c4 50 > $O/prof_c4.txt 2>&1; tail -24 $O/prof_c4.txt ;;
 c45)
-  timeout 300 python bench.py --workload c5 --steps 200 --warmup 20 > $O/bench_c5.json 2>&1; line $O/bench_c5.json
-  timeout 300 python bench.py --workload c4 --steps 100 --warmup 10 > $O/bench_c4.json 2>&1; line $O/bench_c4.json
-  timeout 300 python bench.py --workload c4 --collapsed --steps 100 --warmup 10 > $O/bench_c4_collapsed.json 2>&1; line $O/bench_c4_collapsed.json ;;
+  timeout 300 python bench.py --full --workload c5 --steps 200 --warmup 20 > $O/bench_c5.json 2>&1; line $O/bench_c5.json
+  timeout 300 python bench.py --full --workload c4 --steps 100 --warmup 10 > $O/bench_c4.json 2>&1; line $O/bench_c4.json
+  timeout 300 python bench.py --full --workload c4 --collapsed --steps 100 --warmup 10 > $O/bench_c4_collapsed.json 2>&1; line $O/bench_c4_collapsed.json ;;
 two_procs_c3m)
   # two processes sharing the one GPU, each a C3 multinomial filter (the merged spacings + reduction launch waits
   # on lower-numbered workgroups only: progress must not depend on every workgroup being resident)
-  (timeout 300 python bench.py --workload c3 --scheme multinomial --steps 100 --warmup 10 --no-profile > $O/c3m_proc_a.json 2>&1 &
-   timeout 300 python bench.py --workload c3 --scheme multinomial --steps 100 --warmup 10 --no-profile > $O/c3m_proc_b.json 2>&1; wait)
+  (timeout 300 python bench.py --full --workload c3 --scheme multinomial --steps 100 --warmup 10 --no-profile > $O/c3m_proc_a.json 2>&1 &
+   timeout 300 python bench.py --full --workload c3 --scheme multinomial --steps 100 --warmup 10 --no-profile > $O/c3m_proc_b.json 2>&1; wait)
   for f in $O/c3m_proc_a.json $O/c3m_proc_b.json; do python - $f <<'PY'
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1]); print(sys.argv[1].split('/')[-1], 'ms/step %.5f'%d['ms_per_step'], 'G/s %.2f'%(d['value']/1e9), 'logLt', d['logLt'][:1])
@@ -93,7 +93,7 @@ PY
   done ;;
 two_ranks)
   # the driver's N = 2 launch line with both ranks on this box's one GPU (RCCL refuses: labelled host fallback)
-  SMC_BENCH_NGPU=1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 20 --warmup 5 > $O/bench_2ranks_1gpu.json 2> $O/bench_2ranks_1gpu.err; line $O/bench_2ranks_1gpu.json; tail -2 $O/bench_2ranks_1gpu.err ;;
+  SMC_BENCH_NGPU=1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 2 --steps 20 --warmup 5 > $O/bench_2ranks_1gpu.json 2> $O/bench_2ranks_1gpu.err; line $O/bench_2ranks_1gpu.json; tail -2 $O/bench_2ranks_1gpu.err ;;
 *)
   echo "unknown stage $w" ;;
 esac; done

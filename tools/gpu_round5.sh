@@ -10,7 +10,7 @@ a)  # strict v2: parity at full size, timings, a kernel trace of the strict C2 s
     tail -15 $O/r14a_pytest_strict.log
     timeout 600 python tools/strict_perf.py > $O/r14a_strict_perf.txt 2>&1; tail -40 $O/r14a_strict_perf.txt
     cd /tmp && export TMPDIR=/tmp
-    timeout 200 rocprofv3 --kernel-trace --stats -d $O/trace_c2_strict -o trace -- python $R/bench.py --workload c2 --strict --steps 200 --warmup 20 --reps 3 --no-cpu-baseline --no-other-workloads --no-profile > $O/r14a_c2_strict_trace.log 2>&1
+    timeout 200 rocprofv3 --kernel-trace --stats -d $O/trace_c2_strict -o trace -- python $R/bench.py --full --workload c2 --strict --steps 200 --warmup 20 --reps 3 --no-cpu-baseline --no-other-workloads --no-profile > $O/r14a_c2_strict_trace.log 2>&1
     python $R/tools/summarise_prof.py $O/trace_c2_strict > $O/r14a_c2_strict_summary.txt 2>&1; head -20 $O/r14a_c2_strict_summary.txt
     tail -2 $O/r14a_c2_strict_trace.log
     rm -rf $O/trace_c2_strict
@@ -18,8 +18,8 @@ a)  # strict v2: parity at full size, timings, a kernel trace of the strict C2 s
 full)  # the whole GPU suite, the driver's bench line, K = 1000, the profiles of every leg
     timeout 900 python -m pytest tests -m gpu -x -q > $O/${TAG:-r14}_pytest_gpu.log 2>&1; echo "pytest rc $?" >> $O/${TAG:-r14}_pytest_gpu.log
     tail -6 $O/${TAG:-r14}_pytest_gpu.log
-    timeout 600 python bench.py --steps 20 --warmup 5 > $O/${TAG:-r14}_bench_driver_line.json 2> $O/${TAG:-r14}_bench_driver_line.err; echo "bench rc $?"
-    timeout 300 python bench.py --steps 1000 --warmup 50 --no-other-workloads --no-cpu-baseline > $O/${TAG:-r14}_bench_c2_k1000.json 2>/dev/null
+    timeout 600 python bench.py --full --steps 20 --warmup 5 > $O/${TAG:-r14}_bench_driver_line.json 2> $O/${TAG:-r14}_bench_driver_line.err; echo "bench rc $?"
+    timeout 300 python bench.py --full --steps 1000 --warmup 50 --no-other-workloads --no-cpu-baseline > $O/${TAG:-r14}_bench_c2_k1000.json 2>/dev/null
     python - <<PY
 import json
 d = json.load(open("$O/${TAG:-r14}_bench_driver_line.json"))

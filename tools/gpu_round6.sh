@@ -7,7 +7,7 @@ mkdir -p $O
 cd $R
 c4line() {   # $1 = label, rest = env assignments
   local lab=$1; shift
-  env "$@" timeout 300 python bench.py --workload c4 $C4ARGS --steps 40 --warmup 10 --reps 5 --no-cpu-baseline --no-other-workloads > $O/c4_$lab.json 2>$O/c4_$lab.err
+  env "$@" timeout 300 python bench.py --full --workload c4 $C4ARGS --steps 40 --warmup 10 --reps 5 --no-cpu-baseline --no-other-workloads > $O/c4_$lab.json 2>$O/c4_$lab.err
   python - $O/c4_$lab.json $lab <<'PY'
 import json,sys
 try:
@@ -25,7 +25,7 @@ legab)  # same-box A/B of one bench leg: $2 = bench args, $3 = "label:ENV=1,ENV2
     for rep in 1 2; do
       for item in $3; do
         lab=${item%%:*}; spec=${item#*:}
-        env ${spec//,/ } timeout 300 python bench.py $2 --no-cpu-baseline --no-other-workloads > $O/ab_${lab}_$rep.json 2>$O/ab_${lab}_$rep.err
+        env ${spec//,/ } timeout 300 python bench.py --full $2 --no-cpu-baseline --no-other-workloads > $O/ab_${lab}_$rep.json 2>$O/ab_${lab}_$rep.err
         python - $O/ab_${lab}_$rep.json $lab <<'PY'
 import json,sys
 try:
@@ -54,8 +54,8 @@ tests)
 full)  # the whole GPU suite, the driver's bench line, K = 1000
     timeout 1500 python -m pytest tests -m gpu -x -q > $O/${TAG}_pytest_gpu.log 2>&1; echo "pytest rc $?" >> $O/${TAG}_pytest_gpu.log
     tail -6 $O/${TAG}_pytest_gpu.log
-    timeout 900 python bench.py --steps 20 --warmup 5 > $O/${TAG}_bench_driver_line.json 2> $O/${TAG}_bench_driver_line.err; echo "bench rc $?"
-    timeout 300 python bench.py --steps 1000 --warmup 50 --no-other-workloads --no-cpu-baseline > $O/${TAG}_bench_c2_k1000.json 2>/dev/null
+    timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/${TAG}_bench_driver_line.json 2> $O/${TAG}_bench_driver_line.err; echo "bench rc $?"
+    timeout 300 python bench.py --full --steps 1000 --warmup 50 --no-other-workloads --no-cpu-baseline > $O/${TAG}_bench_c2_k1000.json 2>/dev/null
     python - <<PY
 import json
 d = json.load(open("$O/${TAG}_bench_driver_line.json"))
@@ -67,7 +67,7 @@ print("C2 K=1000", d["value"] / 1e9, d["ms_per_step"])
 PY
     ;;
 line)  # the driver's bench line only
-    timeout 900 python bench.py --steps 20 --warmup 5 > $O/${TAG}_bench_driver_line.json 2> $O/${TAG}_bench_driver_line.err; echo "bench rc $?"
+    timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/${TAG}_bench_driver_line.json 2> $O/${TAG}_bench_driver_line.err; echo "bench rc $?"
     python - <<PY
 import json
 d = json.load(open("$O/${TAG}_bench_driver_line.json"))

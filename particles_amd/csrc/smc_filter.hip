@@ -14,84 +14,253 @@
 // host side
 // ---------------------------------------------------------------------------
 #define PROF_MAX 4096
+#define F_OPT 4        /* new particles per thread of k_propagate */
+#define F_WIDE_TPW 2   /* tiles per workgroup of k_ancestors2w (C2: 17.6 us per step, 4 tiles 18.3, one tile 18.1: profiles/r12d) */
+
+// The step plan: which launches one time step of this filter makes.  plan_step decides it once, in
+// smc_filter_create; enqueue_step, smc_filter_describe, small_filter_ok and smc_filter_step read it and decide
+// nothing themselves.  What may change after create stays an input of the call: a.ut (smc_filter_set_replay: the
+// uniforms come from a tape, no spacings launches), f->prof, whether the step's time index is known (graph capture).
+//
+//   kind            resampling part of the step                                          step record
+//   STEP_FLAT       [SQMC prologue] [k_mv_aux, k_mv_aux_restate] [k_prepare] [spacings: three passes]
+//                   k_ancestors [k_sqmv_compose]                                          k_propagate's tail
+//   STEP_TWO_LEVEL  [reduce] [spacings: one pass (+ reduce merged) | three passes] k_ancestors2 | k_ancestors2w
+//                                                                                         two-level (k_flush2)
+//   STEP_STRICT     [reduce] [spacings: one pass (+ reduce merged) | per island] then by strict_form
+//                   literal:   k_strict_W, k_strict_cdf, k_strict_search_S
+//                   two-level: k_strict_classify, k_strict_search
+//                   array:     k_strict_W, k_sqx_classify, k_sqx_fill, k_strict_search_S      as two_level says
+//   STEP_SQMC       t = 0: k_sq_init; else sort, k_sq_permute, reduce, k_ancestors2<tape, sorted positions>
+//                                                                                         two-level
+//   every kind then: k_propagate | k_propagate_mv, [k_flush2 (two-level record)], [moments kernels]
+//
+// Which combinations exist:
+//   * two_level: univariate, 2 tiles <= N <= 2^30, neither SMC_PATH_FLAT_CDF nor SMC_PATH_FORCE_UNFUSED.  STEP_TWO_LEVEL
+//     and STEP_SQMC always are; STEP_STRICT is where the filter would be otherwise; STEP_FLAT never is (MVLINGAUSS,
+//     one tile, N > 2^30, the two test flags).
+//   * SQMC (SMC_FLAG_SQMC; the scheme is multinomial over a tape of sorted points, every step resamples): univariate
+//     N = 2^k >= 2 tiles is STEP_SQMC; MVLINGAUSS and N < 2 tiles are STEP_FLAT with sq_flat.  Never strict.
+//   * reduce: REDUCE_NONE where the resampling kernel's workgroups reduce the island's partials themselves (resident
+//     grid of at most 1024 tiles per island, closed-form counts, no APF); otherwise a launch opens the step --
+//     k_reduce2w for islands of 1025 .. 4096 tiles (the same bits from 1024 threads), k_reduce2 for the rest, for the
+//     APF's two sets of partials and under SMC_PATH_NO_WIDE.  Always with multinomial counts, SQMC, the strict literal
+//     walk on a two-level record; never on a flat record.
+//   * spacings (multinomial scheme with Philox draws only: SP_NONE for the other schemes and for SQMC):
+//     SP_ONEPASS[_MERGED] needs two_level and a launch that stays resident (sp_tpw tiles of draws per workgroup, sp_nwg
+//     workgroups per island), not the strict literal walk, not SMC_PATH_SPACING_3PASS; _MERGED (the reduction is
+//     workgroup 0 of that launch while the time index is known) also needs eager launches and no
+//     SMC_PATH_SPLIT_REDUCE.  Otherwise SP_THREE_PASS, or SP_PER_ISLAND under STEP_STRICT.
+//   * resampler: RS_PREPARE / RS_FUSED (k_ancestors; fused while every workgroup is resident) without two_level,
+//     RS_TILE / RS_WIDE with it.  RS_WIDE (k_ancestors2w) only under STEP_TWO_LEVEL with reduce == REDUCE_NONE: N = 2^k
+//     with an even number of tiles (either closed-form scheme) or any other N under the systematic scheme; SMC_PATH_NO_WIDE
+//     keeps RS_TILE.  The template arguments come from a.log2N (POW2) and a.scheme.
+//   * small: N <= 1024, univariate, no moments: smc_filter_step runs k_filter_small instead of any of the above unless
+//     profiling is on or the draws are Philox multinomial (small_filter_ok); SMC_PATH_NO_SMALL, strict and SQMC never do.
+enum StepKind { STEP_FLAT, STEP_TWO_LEVEL, STEP_STRICT, STEP_SQMC };
+enum StrictForm { STRICT_LITERAL, STRICT_TWO_LEVEL, STRICT_ARRAY };
+enum ReduceKernel { REDUCE_NONE, REDUCE_NARROW, REDUCE_WIDE };
+enum Spacings { SP_NONE, SP_ONEPASS, SP_ONEPASS_MERGED, SP_THREE_PASS, SP_PER_ISLAND };
+enum Resampler { RS_PREPARE, RS_FUSED, RS_TILE, RS_WIDE };
+
+struct StepPlan {
+    StepKind kind = STEP_FLAT;
+    bool two_level = false;        // the step record is the two-level one: tail-free k_propagate, k_flush2, a.kform
+    bool sq_flat = false;          // STEP_FLAT behind the SQMC prologue / epilogue
+    StrictForm strict_form = STRICT_ARRAY;
+    ReduceKernel reduce = REDUCE_NONE;
+    Spacings spacings = SP_NONE;
+    int sp_tpw = 0, sp_nwg = 0;    // (copied into the argument block: the kernel reads them)
+    Resampler resampler = RS_PREPARE;
+    int ragged = 0;                // two-level record with N not a multiple of the tile: 1 (N even), 2 (N odd or history
+                                   // slots), else 0 (k_propagate<.., RAGGED>)
+    bool xcd_chunks = false;       // consecutive tiles on one XCD (f_tile_xcd; copied into the argument block)
+    bool heavy_list = false;       // heavy parents registered by the resampling kernel (a.hcnt, a.hlist)
+    bool apf2 = false;             // APF on the two-level record: the reduction forms two sets of partials (a.pm2 ..)
+    bool small = false;            // the one-launch filter may run (see small_filter_ok)
+    bool sq_recompute = false;     // STEP_SQMC: sorted weights recomputed from the sorted keys (k_sq_permute<.., true>)
+    bool mv_collapsed = false;     // MVLINGAUSS guided: log G = log p(y_t | x_{t-1}) in one product (opts.flags)
+    bool no_tk = false;            // SMC_PATH_NO_TK: kernels never start on the host's time index (A/B)
+
+    bool strict() const { return kind == STEP_STRICT; }
+    bool sqmc() const { return kind == STEP_SQMC || sq_flat; }
+};
 
 struct smc_filter {
-    smc_ctx* ctx;
+    smc_ctx* ctx = nullptr;
     FArgs a;               // the argument block: passed BY VALUE (kernarg segment: one scalar-load hop,
                            // and the compiler knows its pointers address global memory)
-    int kind, fk;
-    i64 t_host;
-    void* slab;            // one allocation holding every device array
-    size_t slab_bytes;
-    bool use_graph;
-    bool fused;            // k_ancestors<true> (no k_prepare launch)
-    bool two_level;        // k_ancestors2 + tail-free k_propagate (two-level CDF, no intra-launch exchange)
-    bool reduce_narrow;    // SMC_PATH_NO_WIDE: k_reduce2 also where k_reduce2w would run (the A/B the tests compare)
-    bool two_level_mid;    // ... with k_reduce2 in front (grids too large for every workgroup to reduce)
-    int ragged;            // two-level step with N not a multiple of the tile: 1 (N even), 2 (N odd), else 0
-                           // (k_propagate<.., RAGGED>)
-    bool mv_collapsed;     // MVLINGAUSS guided: log G = log p(y_t | x_{t-1}) in one product (opts.flags)
-    bool strict;           // SMC_FLAG_STRICT_ANCESTORS: sequential fp64 CDF of the filter's weights
-    double* strict_ws;     // (n_islands, N) W | (n_islands, N) S | scratch of smc_seqsum.h
-    bool strict_literal;   // SMC_PATH_STRICT_LITERAL: S by the one-lane walk, in place
-    bool sq_plan_zero;     // SQMC: the sort workspace's plan words are zero (smc_rs_sort_ws leaves them so)
+    StepPlan plan;
+    int kind = 0, fk = 0;
+    i64 t_host = 0;
+    void* slab = nullptr;  // one allocation holding every device array
+    size_t slab_bytes = 0;
+    bool use_graph = false;
+    double* strict_ws = nullptr;   // (n_islands, N) W | (n_islands, N) S | scratch of smc_seqsum.h
+    bool sq_plan_zero = false;     // SQMC: the sort workspace's plan words are zero (smc_rs_sort_ws leaves them so)
+    u64 sp_epoch = 0;      // launches of the merged spacings + reduction kernel so far (see FArgs::sp_epoch)
+    bool flush_pending = false;    // two-level record: the summary row of the last step enqueued is still to be written
+                                   // (k_flush2 on demand)
     // SMC_FLAG_SQMC (smc_filter_sqmc.h): the point stream, the tape of ndtri(second coordinate), the
     // sort's workspace and -- more than one island -- the islands' permutations
-    u64 sp_epoch;          // launches of the merged spacings + reduction kernel so far (see FArgs::sp_epoch)
-    bool sp_merge;
-    bool flush_pending;    // two-level step: the summary row of the last step enqueued is still to be written (k_flush2 on demand)
-    bool sqmc, sq_gather;
-    bool sq_flat;          // SQMC on the flat step (multivariate filters; univariate ones below two tiles)
-    u64 sq_seed, sq_ctr0;
-    double* sq_z;
-    u64* sq_perm;
-    void* sq_ws;
-    i64 perm_t;            // t_host at the last smc_filter_permute_islands (A / Xp undefined there)
-    hipGraphExec_t gexec[3];   // captured step sequences of F_GRAPH_SIZES steps (even: see enqueue_step)
-    bool graph_failed;
-    bool prof;
+    u64 sq_seed = 0, sq_ctr0 = 1;
+    double* sq_z = nullptr;
+    u64* sq_perm = nullptr;
+    void* sq_ws = nullptr;
+    i64 perm_t = -1;       // t_host at the last smc_filter_permute_islands (A / Xp undefined there)
+    hipGraphExec_t gexec[3] = {nullptr, nullptr, nullptr};   // captured step sequences of F_GRAPH_SIZES steps (even: see
+                                                             // enqueue_step)
+    bool graph_failed = false;
+    bool prof = false;
     std::vector<hipEvent_t> ev;
-    int prof_n;
-    bool no_tk;            // SMC_PATH_NO_TK: kernels never start on the host's time index (A/B)
-    bool no_small;         // SMC_PATH_NO_SMALL
-    int wide_tpw;          // k_ancestors2w: tiles per workgroup (0: k_ancestors2, one tile per workgroup)
-    double* tmp;           // (N,) staging for W / Xp downloads
-    double* ll_stage;      // (n_islands,) staging for smc_filter_logLt: PINNED host memory the
-                           // collect kernel writes straight into (no copy engine, no staging)
+    int prof_n = 0;
+    double* tmp = nullptr;         // (N,) staging for W / Xp downloads
+    double* ll_stage = nullptr;    // (n_islands,) staging for smc_filter_logLt: PINNED host memory the
+                                   // collect kernel writes straight into (no copy engine, no staging)
     // SMC^2 theta level (smc_filter_theta_enable): theta log-weights, stop record, ESS log
-    double *lwth, *th, *th_ess;
-    double th_ess_min;
-    void* th_buf;
+    double *lwth = nullptr, *th = nullptr, *th_ess = nullptr;
+    double th_ess_min = 0.0;
+    void* th_buf = nullptr;
     // ... of a population sharded over ranks (smc_filter_theta_enable_sharded): the theta level is
     // replicated -- th_n = nranks x n_islands log-weights on every rank -- and fed by an all-gather of the
     // ranks' evidence increments enqueued behind every step
-    smc_comm* th_comm;
-    int th_n;
-    double *th_send, *th_recv;
+    smc_comm* th_comm = nullptr;
+    int th_n = 0;
+    double *th_send = nullptr, *th_recv = nullptr;
 };
 
-typedef void (*move_fn)(FArgs);
+// the uniforms of a multinomial step are drawn on the device (no replay tape: smc_filter_set_replay may set one later)
+static bool philox_multinomial(const FArgs& a) { return a.scheme == SMC_MULTINOMIAL && !a.ut; }
 
-// the island's reduction as a launch of its own: islands of 1025 .. 4096 tiles by a workgroup of 1024 threads (k_reduce2w:
-// the same bits), anything else -- and the APF's two sets of partials -- by k_reduce2
+// SMC_FLAG_SQMC on the flat step: multivariate filters; univariate ones below two tiles
+static bool sqmc_on_flat_step(const smc_model* model, const smc_filter_opts* o)
+{
+    return model->kind == SMC_MODEL_MVLINGAUSS || o->N < 2 * F_TILE;
+}
+
+// Fills the plan from the model, the options and the shape words of the argument block (N, n_islands, ntiles,
+// nparts, log2N, hist, scheme).  Nothing is allocated yet; the device is current (the occupancy query).
+static int plan_step(const smc_ctx* ctx, const smc_model* model, const smc_filter_opts* o, const FArgs& a, StepPlan* out)
+{
+    const unsigned flags = (unsigned)o->flags;
+    const bool mv = model->kind == SMC_MODEL_MVLINGAUSS;
+    const bool strict = (flags & SMC_FLAG_STRICT_ANCESTORS) != 0, literal = (flags & SMC_PATH_STRICT_LITERAL) != 0;
+    const bool sqmc = (flags & SMC_FLAG_SQMC) != 0;
+    const i64 M = a.n_islands;
+    StepPlan p;
+    p.sq_flat = sqmc && sqmc_on_flat_step(model, o);
+    // two-level CDF: closed-form offspring counts (N = 2^k with integers, other N with the general counts; systematic /
+    // stratified), at least 2 tiles (below, the one-workgroup filter)
+    // (multinomial: the counts are searches over the sorted uniforms -- the tape's, or the exponential
+    //  spacings drawn between the reduction, which decides the step, and k_ancestors2)
+    p.two_level = !mv && o->N <= ((int64_t)1 << 30) && a.ntiles >= 2 && !(flags & (SMC_PATH_FLAT_CDF | SMC_PATH_FORCE_UNFUSED));
+    p.apf2 = !mv && f_is_apf(model->fk) && o->N > F_TILE;
+    if (p.apf2 && !p.two_level) {
+        smc_set_error("the auxiliary particle filter beyond N = 1024 runs on the two-level step only");
+        return SMC_ERR_INVALID;
+    }
+    if (sqmc && !p.sq_flat && !p.two_level) {
+        smc_set_error("SMC_FLAG_SQMC needs the two-level step");
+        return SMC_ERR_INVALID;
+    }
+    p.kind = (sqmc && !p.sq_flat) ? STEP_SQMC : strict ? STEP_STRICT : p.two_level ? STEP_TWO_LEVEL : STEP_FLAT;
+    p.strict_form = literal ? STRICT_LITERAL : p.two_level ? STRICT_TWO_LEVEL : STRICT_ARRAY;
+    // (published tile totals pay off only while every workgroup of the launch is resident; SMC_PATH_FORCE_UNFUSED
+    //  (tests): the k_prepare path at any size)
+    const bool resident = (i64)a.ntiles * M <= F_DIRECT_PREFIX_MAX && !(flags & SMC_PATH_FORCE_UNFUSED);
+    // every workgroup reduces the partials itself while the launch is resident and an island has
+    // at most 1024 tiles (4 per thread); otherwise one workgroup per island does it first
+    const bool mid = p.two_level && (!resident || a.ntiles > 1024 || (flags & SMC_PATH_TWO_LEVEL_MID) ||
+                                     a.scheme == SMC_MULTINOMIAL || p.apf2);
+    if (p.two_level && (mid || (strict && literal))) {
+        const int nchunks = (a.nparts + 4 * SMC_BLOCK - 1) / (4 * SMC_BLOCK);
+        p.reduce = (nchunks >= 2 && nchunks <= 4 && !p.apf2 && !(flags & SMC_PATH_NO_WIDE)) ? REDUCE_WIDE : REDUCE_NARROW;
+    }
+    // resident grids: F_WIDE_TPW tiles per workgroup (smc_filter_wide.h) -- N = 2^k with whole pairs of tiles, any other N
+    // under the systematic scheme (the general counts: the last workgroup of a run may hold one tile);
+    // SMC_PATH_NO_WIDE keeps the one-tile kernel testable at these sizes
+    const bool wide = p.kind == STEP_TWO_LEVEL && !mid && !(flags & SMC_PATH_NO_WIDE) &&
+                      (a.log2N >= 0 ? a.ntiles % F_WIDE_TPW == 0 : a.scheme == SMC_SYSTEMATIC);
+    p.resampler = p.two_level ? (wide ? RS_WIDE : RS_TILE) : (resident ? RS_FUSED : RS_PREPARE);
+    // consecutive tiles on one XCD (f_tile_xcd): any number of tiles with one tile per resampling workgroup; with
+    // k_ancestors2w whole multiples of 8 x (its tiles per workgroup) -- else the wide kernel keeps its own XCD-strided map
+    p.xcd_chunks = p.kind == STEP_TWO_LEVEL && !(flags & SMC_PATH_NO_XCD_CHUNKS) && a.ntiles >= 16 &&
+                   (!wide || a.log2N < 0 || a.ntiles % (8 * F_WIDE_TPW) == 0);
+    // (measured and kept out, round 4: the reduction MERGED into the resampling launch on grids beyond 2048 workgroups --
+    //  (a) every workgroup of k_ancestors2w reducing: C5 99.2 us per step (2 tiles per workgroup) / 117.2 (4) against 92.9
+    //  behind k_reduce2 (r12h); (b) workgroup 0 of k_ancestors2 reducing, the others waiting for its word with their
+    //  loads in flight and reading (G_b, Q_b) past their L2: C3 60.7 against 57.6 us, C5 159 against 99 -- a dependent
+    //  global round trip in every workgroup costs more than the launch it saves (r12j))
+    // (SQMC: k_ancestors2 counts in SORTED positions; a heavy parent's blocks would be filled with that index)
+    p.heavy_list = !mv && !strict && !sqmc && !(flags & SMC_PATH_NO_HEAVY);
+    // (history slots are written step by step: the lanes beyond N of a slot would read indices nobody
+    //  initialised -- every access tests its index there as well)
+    p.ragged = (p.two_level && (o->N % F_TILE) != 0) ? (((o->N & 1) || a.hist) ? 2 : 1) : 0;
+    // one-pass uniform_spacings (two-level record, Philox draws): 1, 2, 4 or 8 tiles of draws per workgroup,
+    // the fewest that keep the whole launch resident (<= 1024 workgroups: half of what the chip holds);
+    // more islands than that: the three-pass form
+    bool merge_fits = false;
+    if (a.scheme == SMC_MULTINOMIAL && p.two_level && !(strict && literal) && !sqmc && !(flags & SMC_PATH_SPACING_3PASS))
+        for (int tpw = 1; tpw <= 8 && !p.sp_tpw; tpw *= 2) {
+            const int forced_tpw = (o->flags >> 25) & 15;          // SMC_PATH_SP_TPW (A/B: workgroups wait for
+            if (forced_tpw && tpw != forced_tpw) continue;         //  lower-numbered ones only, dispatch is in order)
+            const i64 nwg = (a.ntiles + tpw - 1) / tpw;
+#ifdef SMC_EMULATE
+            const i64 cap = 1024, cap_merged = ((i64)1 << 62);     // (workgroups run one after the other, in order)
+            (void)ctx;
+#else
+            int per_cu = 0;                        // workgroups of this instantiation a CU holds at once
+            const void* fn = tpw == 1 ? (const void*)k_f_spacing_onepass<1> : tpw == 2 ? (const void*)k_f_spacing_onepass<2>
+                           : tpw == 4 ? (const void*)k_f_spacing_onepass<4> : (const void*)k_f_spacing_onepass<8>;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, SMC_BLOCK, 0) != hipSuccess) per_cu = 0;
+            (void)hipGetLastError();
+            // (a margin of one workgroup per CU: the occupancy API is optimistic near register-file edges)
+            const i64 cap = (i64)(per_cu > 1 ? per_cu - 1 : 0) * ctx->n_cu, cap_merged = (i64)per_cu * ctx->n_cu;
+#endif
+            if ((nwg * M <= cap && nwg * M <= 1024) || (forced_tpw && nwg <= 1024)) {
+                p.sp_tpw = tpw;
+                p.sp_nwg = (int)nwg;
+                // one workgroup more per island when the reduction rides along: it is the first of the launch and
+                // waits for nobody, the others wait for lower-numbered ones only -- dispatch is in order, so the
+                // margin kept above is not needed for it, the chip's nominal capacity is
+                merge_fits = (nwg + 1) * M <= cap_merged || forced_tpw;
+            }
+        }
+    // (inside a replayed graph the argument block -- the epoch with it -- is frozen: separate launches there)
+    const bool merge = p.sp_tpw && merge_fits && !o->use_graph && !(flags & SMC_PATH_SPLIT_REDUCE);
+    p.spacings = (a.scheme != SMC_MULTINOMIAL || sqmc) ? SP_NONE
+                 : p.sp_tpw ? (merge ? SP_ONEPASS_MERGED : SP_ONEPASS)
+                 : strict ? SP_PER_ISLAND : SP_THREE_PASS;
+    p.small = o->N <= F_TILE && !mv && !o->moments && !strict && !sqmc && !(flags & SMC_PATH_NO_SMALL);
+    // bootstrap filters whose weight depends on the new particle only: the sorted weights are recomputed
+    // from the sorted keys; SMC_PATH_SQ_GATHER (A/B) and the others gather them
+    // (one island, N beyond the one-workgroup sort: the workspace then holds the key images of that island)
+    p.sq_recompute = model->fk == SMC_FK_BOOTSTRAP && model->kind != SMC_MODEL_SVLEVERAGE && !(flags & SMC_PATH_SQ_GATHER) &&
+                     a.n_islands == 1 && a.N > 2048;
+    p.mv_collapsed = mv && model->fk == SMC_FK_GUIDED && (flags & SMC_FLAG_COLLAPSED_PROPOSAL);
+    p.no_tk = (flags & SMC_PATH_NO_TK) != 0;
+    *out = p;
+    return SMC_OK;
+}
+
+// the island's reduction as a launch of its own (plan.reduce)
 static void launch_reduce2(smc_filter* f, hipStream_t st)
 {
-    const int nchunks = (f->a.nparts + 4 * SMC_BLOCK - 1) / (4 * SMC_BLOCK);
-    if (nchunks >= 2 && nchunks <= 4 && !f->a.pm2 && !f->reduce_narrow)
+    if (f->plan.reduce == REDUCE_WIDE)
         SMC_LAUNCH(k_reduce2w, dim3(f->a.n_islands), dim3(4 * SMC_BLOCK), st, f->a);
     else
         SMC_LAUNCH(k_reduce2, dim3(f->a.n_islands), dim3(SMC_BLOCK), st, f->a);
 }
 
-#define F_OPT 4     /* new particles per thread of k_propagate */
-
 static void launch_propagate(smc_filter* f)
 {
     hipStream_t st = f->ctx->stream;
     const dim3 grid(f->a.nparts, f->a.n_islands);
+    const bool two_level = f->plan.two_level;
+    const int ragged = f->plan.ragged;
     if (f->kind == SMC_MODEL_MVLINGAUSS) {
 #define MV_CASE(FKV, DPV, COLLV)                                                            \
-    if (f->fk == FKV && f->a.dp == DPV && f->mv_collapsed == COLLV) {                       \
+    if (f->fk == FKV && f->a.dp == DPV && f->plan.mv_collapsed == COLLV) {                  \
         if (f->a.dx == DPV && f->a.mv_diag)                                                 \
             SMC_LAUNCH((k_propagate_mv<FKV, DPV, true, COLLV, true>), grid, dim3(SMC_BLOCK), st,  \
                        f->a, f->a.mvc);                                                     \
@@ -117,17 +286,17 @@ static void launch_propagate(smc_filter* f)
 #define P_LEAD f->a.A, f->a.info, f->a.params, f->a.hcnt, f->a.N, f->a.ntiles | (f->a.xcd_chunks ? 1 << 30 : 0)
 #define P_CASE(KINDV, FKV)                                                                    \
     if (f->kind == KINDV && f->fk == FKV) {                                                   \
-        if (f->two_level && f->ragged == 1 && f->a.par >= 0)                                  \
+        if (two_level && ragged == 1 && f->a.par >= 0)                                        \
             SMC_LAUNCH((k_propagate<KINDV, FKV, F_OPT, true, false, 1>), grid, dim3(SMC_BLOCK), st, P_LEAD, f->a);  \
-        else if (f->two_level && f->ragged == 1)                                              \
+        else if (two_level && ragged == 1)                                                    \
             SMC_LAUNCH((k_propagate<KINDV, FKV, F_OPT, false, false, 1>), grid, dim3(SMC_BLOCK), st, P_LEAD, f->a); \
-        else if (f->two_level && f->ragged == 2 && f->a.par >= 0)                             \
+        else if (two_level && ragged == 2 && f->a.par >= 0)                                   \
             SMC_LAUNCH((k_propagate<KINDV, FKV, F_OPT, true, false, 2>), grid, dim3(SMC_BLOCK), st, P_LEAD, f->a);  \
-        else if (f->two_level && f->ragged == 2)                                              \
+        else if (two_level && ragged == 2)                                                    \
             SMC_LAUNCH((k_propagate<KINDV, FKV, F_OPT, false, false, 2>), grid, dim3(SMC_BLOCK), st, P_LEAD, f->a); \
-        else if (f->two_level && f->a.par >= 0)                                               \
+        else if (two_level && f->a.par >= 0)                                                  \
             SMC_LAUNCH((k_propagate<KINDV, FKV, F_OPT, true, false>), grid, dim3(SMC_BLOCK), st, P_LEAD, f->a);  \
-        else if (f->two_level)                                                                \
+        else if (two_level)                                                                   \
             SMC_LAUNCH((k_propagate<KINDV, FKV, F_OPT, false, false>), grid, dim3(SMC_BLOCK), st, P_LEAD, f->a); \
         else if (f->a.par >= 0)                                                               \
             SMC_LAUNCH((k_propagate<KINDV, FKV, F_OPT, true>), grid, dim3(SMC_BLOCK), st, P_LEAD, f->a);  \
@@ -151,53 +320,76 @@ static void launch_propagate(smc_filter* f)
 #undef P_LEAD
 }
 
-static void launch_onepass(const FArgs& a, const dim3 gw, hipStream_t st)
+// uniform_spacings for the Philox draws of a multinomial step, in the plan's form; merge: the island's reduction is
+// workgroup 0 of the one-pass launch
+static void launch_spacings(smc_filter* f, hipStream_t st, bool merge)
 {
-    switch (a.sp_tpw) {
-    case 1: SMC_LAUNCH(k_f_spacing_onepass<1>, gw, dim3(SMC_BLOCK), st, a); break;
-    case 2: SMC_LAUNCH(k_f_spacing_onepass<2>, gw, dim3(SMC_BLOCK), st, a); break;
-    case 4: SMC_LAUNCH(k_f_spacing_onepass<4>, gw, dim3(SMC_BLOCK), st, a); break;
-    default: SMC_LAUNCH(k_f_spacing_onepass<8>, gw, dim3(SMC_BLOCK), st, a); break;
+    const FArgs& a = f->a;
+    const dim3 g1(a.ntiles1, a.n_islands);
+    switch (f->plan.spacings) {
+    case SP_ONEPASS:
+    case SP_ONEPASS_MERGED: {          // decoupled look-back: every workgroup resident
+        const dim3 gw(a.sp_nwg + (merge ? 1 : 0), a.n_islands);
+        switch (a.sp_tpw) {
+        case 1: SMC_LAUNCH(k_f_spacing_onepass<1>, gw, dim3(SMC_BLOCK), st, a); break;
+        case 2: SMC_LAUNCH(k_f_spacing_onepass<2>, gw, dim3(SMC_BLOCK), st, a); break;
+        case 4: SMC_LAUNCH(k_f_spacing_onepass<4>, gw, dim3(SMC_BLOCK), st, a); break;
+        default: SMC_LAUNCH(k_f_spacing_onepass<8>, gw, dim3(SMC_BLOCK), st, a); break;
+        }
+        break;
+    }
+    case SP_THREE_PASS:                // two passes over the same draws (tile sums, their prefixes, the uniforms written once)
+        SMC_LAUNCH(k_f_spacing_sums, g1, dim3(SMC_BLOCK), st, a);
+        SMC_LAUNCH(k_f_spacing_scan, dim3(a.n_islands), dim3(SMC_BLOCK), st, a);
+        SMC_LAUNCH(k_f_spacing_write, g1, dim3(SMC_BLOCK), st, a);
+        break;
+    case SP_PER_ISLAND:                // (the strict literal walk and one-tile strict filters)
+        for (int i = 0; i < a.n_islands; ++i)
+            SMC_LAUNCH(k_f_spacings_step, dim3(1), dim3(SMC_BLOCK), st, a, i, a.su + (size_t)i * a.N);
+        break;
+    case SP_NONE: break;
     }
 }
 
-// one time step: [k_prepare, (spacings), k_ancestors] do nothing unless the step
-// resamples (decided on the device by the previous k_propagate), then k_propagate
-static void enqueue_step(smc_filter* f, int k_prof, i64 t, bool t_known = true)
+// the step's sorted uniforms are drawn on the device: multinomial scheme, Philox mode, no replay tape set since
+static bool draws_spacings(const smc_filter* f) { return f->plan.spacings != SP_NONE && !f->a.ut; }
+
+// what opens a two-level or strict step: the island's reduction (decision + normalisation of step t-1) and the
+// spacings -- the reduction as a launch of its own, or as workgroup 0 of the one-pass spacings kernel
+static void open_step(smc_filter* f, hipStream_t st, bool t_known)
 {
-    // the host knows the time index of every step it enqueues; inside a replayed graph
-    // only its parity is static (graphs hold an even number of steps and start at even t)
-    f->a.par = f->a.hist ? -1 : (int)(t & 1);
-    f->a.tk = (t_known && !f->no_tk) ? t : -1;
-    hipStream_t st = f->ctx->stream;
-    const dim3 grid(f->a.ntiles, f->a.n_islands);
-    if (k_prof >= 0) (void)hipEventRecord(f->ev[3 * k_prof], st);
-    if (f->sqmc && !f->sq_flat) {
-        // smc_filter_sqmc.h.  The step's normals come from a tape that is ONE step's buffer (zt_ts = 0),
-        // written by k_sq_init / k_sq_permute just before; the thresholds are a function of n (f2_sq_T)
-        FArgs& a = f->a;
-        a.zt = f->sq_z;
-        a.zt_ts = 0;
-        a.sq_seed = f->sq_seed;
-        a.sq_ctr = f->sq_ctr0;
-        // (inside a captured graph only the parity of t is static: replays start at t >= 2, see smc_filter_step)
-        if (t_known && t == 0) {
-            SMC_LAUNCH(k_sq_init, dim3((unsigned)((a.N + SMC_BLOCK - 1) / SMC_BLOCK), a.n_islands), dim3(SMC_BLOCK), st,
-                       f->a, f->sq_z, f->sq_seed, f->sq_ctr0);
-        } else {
-            // bootstrap filters whose weight depends on the new particle only: the sorted weights are recomputed
-            // from the sorted keys (k_sq_permute<.., true>); SMC_PATH_SQ_GATHER (A/B) and the others gather them
-            // (one island, N beyond the one-workgroup sort: the workspace then holds the key images of that island)
-            const bool recompute = f->fk == SMC_FK_BOOTSTRAP && f->kind != SMC_MODEL_SVLEVERAGE && !f->sq_gather &&
-                                   a.n_islands == 1 && a.N > 2048;
-            const u64 *perm = f->sq_perm, *skeys = nullptr;
-            for (int i = 0; i < a.n_islands; ++i) {        // h_order = argsort(X_{t-1}) (hilbert.py:52-54, d = 1)
-                u64 *k0 = nullptr, *v0 = nullptr;
-                (void)smc_rs_sort_ws(f->ctx, f_X(a, t - 1) + (i64)i * a.N, nullptr, a.N, 0, f->sq_ws, recompute ? &k0 : nullptr, &v0, f->sq_plan_zero);
-                f->sq_plan_zero = true;               // (every sort leaves its plan words zeroed for the next)
-                if (a.n_islands == 1) { perm = v0; skeys = k0; }
-                else (void)hipMemcpyAsync(f->sq_perm + (i64)i * a.N, v0, (size_t)a.N * 8, hipMemcpyDeviceToDevice, st);
-            }
+    const bool draws = draws_spacings(f);
+    const bool merge = draws && f->plan.spacings == SP_ONEPASS_MERGED && t_known;
+    f->a.sp_epoch = merge ? ++f->sp_epoch : 0ull;
+    if (f->plan.reduce != REDUCE_NONE && !merge) launch_reduce2(f, st);
+    if (draws) launch_spacings(f, st, merge);
+}
+
+// STEP_SQMC (smc_filter_sqmc.h).  The step's normals come from a tape that is ONE step's buffer (zt_ts = 0),
+// written by k_sq_init / k_sq_permute just before; the thresholds are a function of n (f2_sq_T)
+static void resample_sqmc(smc_filter* f, hipStream_t st, i64 t, bool t_known)
+{
+    FArgs& a = f->a;
+    const dim3 grid(a.ntiles, a.n_islands);
+    a.zt = f->sq_z;
+    a.zt_ts = 0;
+    a.sq_seed = f->sq_seed;
+    a.sq_ctr = f->sq_ctr0;
+    // (inside a captured graph only the parity of t is static: replays start at t >= 2, see smc_filter_step)
+    if (t_known && t == 0) {
+        SMC_LAUNCH(k_sq_init, dim3((unsigned)((a.N + SMC_BLOCK - 1) / SMC_BLOCK), a.n_islands), dim3(SMC_BLOCK), st,
+                   f->a, f->sq_z, f->sq_seed, f->sq_ctr0);
+        return;
+    }
+    const bool recompute = f->plan.sq_recompute;
+    const u64 *perm = f->sq_perm, *skeys = nullptr;
+    for (int i = 0; i < a.n_islands; ++i) {        // h_order = argsort(X_{t-1}) (hilbert.py:52-54, d = 1)
+        u64 *k0 = nullptr, *v0 = nullptr;
+        (void)smc_rs_sort_ws(f->ctx, f_X(a, t - 1) + (i64)i * a.N, nullptr, a.N, 0, f->sq_ws, recompute ? &k0 : nullptr, &v0, f->sq_plan_zero);
+        f->sq_plan_zero = true;               // (every sort leaves its plan words zeroed for the next)
+        if (a.n_islands == 1) { perm = v0; skeys = k0; }
+        else (void)hipMemcpyAsync(f->sq_perm + (i64)i * a.N, v0, (size_t)a.N * 8, hipMemcpyDeviceToDevice, st);
+    }
 #define SQ_CASE(KINDV)                                                                                           \
     if (f->kind == KINDV) {                                                                                      \
         if (recompute) SMC_LAUNCH((k_sq_permute<KINDV, true>), grid, dim3(SMC_BLOCK), st, f->a, perm, skeys, f->sq_z, \
@@ -205,192 +397,144 @@ static void enqueue_step(smc_filter* f, int k_prof, i64 t, bool t_known = true)
         else SMC_LAUNCH((k_sq_permute<KINDV, false>), grid, dim3(SMC_BLOCK), st, f->a, perm, skeys, f->sq_z,      \
                         f->sq_seed, f->sq_ctr0);                                                                 \
     }
-            SQ_CASE(SMC_MODEL_LINGAUSS) SQ_CASE(SMC_MODEL_STOCHVOL) SQ_CASE(SMC_MODEL_GORDON)
-            SQ_CASE(SMC_MODEL_THETALOGISTIC) SQ_CASE(SMC_MODEL_SVLEVERAGE) SQ_CASE(SMC_MODEL_DISCRETECOX)
+    SQ_CASE(SMC_MODEL_LINGAUSS) SQ_CASE(SMC_MODEL_STOCHVOL) SQ_CASE(SMC_MODEL_GORDON)
+    SQ_CASE(SMC_MODEL_THETALOGISTIC) SQ_CASE(SMC_MODEL_SVLEVERAGE) SQ_CASE(SMC_MODEL_DISCRETECOX)
 #undef SQ_CASE
-            launch_reduce2(f, st);
-            f->a.sq_perm = perm;                     // (A = h_order[sorted position]: composed where the ancestors are stored)
-            SMC_LAUNCH((k_ancestors2<true, true, true, false, true>), grid, dim3(SMC_BLOCK), st, f->a);
-        }
-        if (k_prof >= 0 && (k_prof % 3)) (void)hipEventRecord(f->ev[3 * k_prof + 1], st);
-        launch_propagate(f);
-        if (k_prof >= 0) (void)hipEventRecord(f->ev[3 * k_prof + 2], st);
-        if (a.mom) {
-            SMC_LAUNCH(k_flush2, dim3(a.n_islands), dim3(SMC_BLOCK), st, f->a);
-            SMC_LAUNCH(k_f_moments_partials, dim3(a.nmb, a.n_islands), dim3(SMC_BLOCK), st, f->a);
-            SMC_LAUNCH(k_f_moments_final, dim3(a.n_islands), dim3(SMC_BLOCK), st, f->a);
-        }
-        return;
-    }
-    if (f->strict) {
-        // decision + normalisation of step t-1 (two-level: by k_strict_classify's workgroups themselves, or k_reduce2
-        // beyond 1024 tiles / for multinomial draws / the literal walk; flat: k_propagate's tail did it), the
-        // sequential CDF of W_{t-1}, the searches
-        // (multinomial, Philox draws: uniform_spacings in one pass, the island's reduction as its workgroup 0 where the
-        //  grid fits -- as on the default path; the literal walk and one-tile filters: one workgroup per island)
-        const bool sp1 = f->a.scheme == SMC_MULTINOMIAL && !f->a.ut && f->a.sp_tpw;
-        const bool merge = sp1 && f->sp_merge && t_known;
-        f->a.sp_epoch = merge ? ++f->sp_epoch : 0ull;
-        if (f->two_level && (f->two_level_mid || f->strict_literal) && !merge)
-            launch_reduce2(f, st);
-        if (sp1) {
-            const dim3 gw(f->a.sp_nwg + (merge ? 1 : 0), f->a.n_islands);
-            switch (f->a.sp_tpw) {
-            case 1: SMC_LAUNCH(k_f_spacing_onepass<1>, gw, dim3(SMC_BLOCK), st, f->a); break;
-            case 2: SMC_LAUNCH(k_f_spacing_onepass<2>, gw, dim3(SMC_BLOCK), st, f->a); break;
-            case 4: SMC_LAUNCH(k_f_spacing_onepass<4>, gw, dim3(SMC_BLOCK), st, f->a); break;
-            default: SMC_LAUNCH(k_f_spacing_onepass<8>, gw, dim3(SMC_BLOCK), st, f->a); break;
-            }
-        } else if (f->a.scheme == SMC_MULTINOMIAL && !f->a.ut) {
-            for (int i = 0; i < f->a.n_islands; ++i)
-                SMC_LAUNCH(k_f_spacings_step, dim3(1), dim3(SMC_BLOCK), st, f->a, i, f->a.su + (size_t)i * f->a.N);
-        }
-        const unsigned nb = (unsigned)((f->a.N + 1023) / 1024);
-        const dim3 gt(nb, f->a.n_islands);
-        // (strict_ws: (n_islands, N) W | (n_islands, N) S | the scratch of smc_seqx.h | (n_islands, ntiles) tile sums)
-        double* S = f->strict_ws + (size_t)f->a.n_islands * f->a.N;
-        void* sqx_scr = (void*)(S + (size_t)f->a.n_islands * f->a.N);
-        SqxArgs q = sqx_carve(sqx_scr, f->a.N, f->a.n_islands);
+    launch_reduce2(f, st);
+    f->a.sq_perm = perm;                     // (A = h_order[sorted position]: composed where the ancestors are stored)
+    SMC_LAUNCH((k_ancestors2<true, true, true, false, true>), grid, dim3(SMC_BLOCK), st, f->a);
+}
+
+// STEP_STRICT: the sequential CDF of W_{t-1} and the searches, behind open_step (flat record: k_propagate's tail
+// decided and normalised)
+static void resample_strict(smc_filter* f, hipStream_t st, bool t_known)
+{
+    open_step(f, st, t_known);
+    const unsigned nb = (unsigned)((f->a.N + 1023) / 1024);
+    const dim3 gt(nb, f->a.n_islands);
+    const dim3 gs((unsigned)((f->a.N / 2 + SMC_BLOCK) / SMC_BLOCK), f->a.n_islands);
+    // (strict_ws: (n_islands, N) W | (n_islands, N) S | the scratch of smc_seqx.h | (n_islands, ntiles) tile sums)
+    double* S = f->strict_ws + (size_t)f->a.n_islands * f->a.N;
+    void* sqx_scr = (void*)(S + (size_t)f->a.n_islands * f->a.N);
+    SqxArgs q = sqx_carve(sqx_scr, f->a.N, f->a.n_islands);
 #ifdef SMC_TRACE
-        q.trace = f->a.trace + (size_t)f->a.n_islands * (f->a.nparts + f->a.ntiles) * 8;
+    q.trace = f->a.trace + (size_t)f->a.n_islands * (f->a.nparts + f->a.ntiles) * 8;
 #endif
-        const SeqGate gate{f->a.info, INFO_STRIDE, f->a.T, nullptr};
-        if (f->strict_literal) {
-            // the definition: W written out, ONE lane adding it up in place (44 ms at N = 2^20), a search per offspring
-            SMC_LAUNCH(k_strict_W, gt, dim3(SMC_BLOCK), st, f->a, f->strict_ws, (double*)nullptr);
-            SMC_LAUNCH(k_strict_cdf, dim3(1, f->a.n_islands), dim3(64), st, f->a, f->strict_ws);
-            SMC_LAUNCH(k_strict_search_S, dim3((unsigned)((f->a.N / 2 + SMC_BLOCK) / SMC_BLOCK), f->a.n_islands), dim3(SMC_BLOCK), st,
-                       f->a, (const double*)f->strict_ws, (const double*)f->a.su);
-        } else if (f->two_level) {
-            // the same doubles in two launches, S never written (smc_filter_strict.h)
-            if (f->two_level_mid) SMC_LAUNCH(k_strict_classify<true>, gt, dim3(SMC_BLOCK), st, f->a, q);
-            else SMC_LAUNCH(k_strict_classify<false>, gt, dim3(SMC_BLOCK), st, f->a, q);
-            SMC_LAUNCH(k_strict_search, gt, dim3(SMC_BLOCK), st, f->a, q);
-        } else {
-            // one tile (or a flat test path): W materialised, the two launches of smc_seqx.h on the array, S written
-            size_t used = 0;
-            (void)sqx_carve(sqx_scr, f->a.N, f->a.n_islands, &used);
-            double* tsum = (double*)((char*)sqx_scr + used);
-            SMC_LAUNCH(k_strict_W, gt, dim3(SMC_BLOCK), st, f->a, f->strict_ws, tsum);
-            SMC_LAUNCH(k_sqx_classify, gt, dim3(SMC_BLOCK), st, (const double*)f->strict_ws, (const double*)tsum, q, gate);
-            SMC_LAUNCH(k_sqx_fill, gt, dim3(SMC_BLOCK), st, q, S, gate);
-            SMC_LAUNCH(k_strict_search_S, dim3((unsigned)((f->a.N / 2 + SMC_BLOCK) / SMC_BLOCK), f->a.n_islands), dim3(SMC_BLOCK), st,
-                       f->a, (const double*)S, (const double*)f->a.su);
-        }
-        if (k_prof >= 0 && (k_prof % 3)) (void)hipEventRecord(f->ev[3 * k_prof + 1], st);
-        launch_propagate(f);
-        if (k_prof >= 0) (void)hipEventRecord(f->ev[3 * k_prof + 2], st);
-        if (f->a.mom) {
-            if (f->two_level) SMC_LAUNCH(k_flush2, dim3(f->a.n_islands), dim3(SMC_BLOCK), st, f->a);
-            SMC_LAUNCH(k_f_moments_partials, dim3(f->a.nmb, f->a.n_islands), dim3(SMC_BLOCK), st, f->a);
-            SMC_LAUNCH(k_f_moments_final, dim3(f->a.n_islands), dim3(SMC_BLOCK), st, f->a);
-        }
+    const SeqGate gate{f->a.info, INFO_STRIDE, f->a.T, nullptr};
+    switch (f->plan.strict_form) {
+    case STRICT_LITERAL:
+        // the definition: W written out, ONE lane adding it up in place (44 ms at N = 2^20), a search per offspring
+        SMC_LAUNCH(k_strict_W, gt, dim3(SMC_BLOCK), st, f->a, f->strict_ws, (double*)nullptr);
+        SMC_LAUNCH(k_strict_cdf, dim3(1, f->a.n_islands), dim3(64), st, f->a, f->strict_ws);
+        SMC_LAUNCH(k_strict_search_S, gs, dim3(SMC_BLOCK), st, f->a, (const double*)f->strict_ws, (const double*)f->a.su);
+        break;
+    case STRICT_TWO_LEVEL:
+        // the same doubles in two launches, S never written (smc_filter_strict.h)
+        if (f->plan.reduce != REDUCE_NONE) SMC_LAUNCH(k_strict_classify<true>, gt, dim3(SMC_BLOCK), st, f->a, q);
+        else SMC_LAUNCH(k_strict_classify<false>, gt, dim3(SMC_BLOCK), st, f->a, q);
+        SMC_LAUNCH(k_strict_search, gt, dim3(SMC_BLOCK), st, f->a, q);
+        break;
+    case STRICT_ARRAY: {
+        // one tile (or a flat test path): W materialised, the two launches of smc_seqx.h on the array, S written
+        size_t used = 0;
+        (void)sqx_carve(sqx_scr, f->a.N, f->a.n_islands, &used);
+        double* tsum = (double*)((char*)sqx_scr + used);
+        SMC_LAUNCH(k_strict_W, gt, dim3(SMC_BLOCK), st, f->a, f->strict_ws, tsum);
+        SMC_LAUNCH(k_sqx_classify, gt, dim3(SMC_BLOCK), st, (const double*)f->strict_ws, (const double*)tsum, q, gate);
+        SMC_LAUNCH(k_sqx_fill, gt, dim3(SMC_BLOCK), st, q, S, gate);
+        SMC_LAUNCH(k_strict_search_S, gs, dim3(SMC_BLOCK), st, f->a, (const double*)S, (const double*)f->a.su);
+        break;
+    }
+    }
+}
+
+// STEP_TWO_LEVEL: k_ancestors2 / k_ancestors2w behind open_step
+static void resample_two_level(smc_filter* f, hipStream_t st, bool t_known)
+{
+    open_step(f, st, t_known);
+    const dim3 grid(f->a.ntiles, f->a.n_islands);
+    if (f->a.scheme == SMC_MULTINOMIAL) {
+        // searches over the sorted uniforms: the spacings just drawn (k_ancestors2 finds its window through the
+        // tile prefixes) or the tape's
+        if (!f->a.ut) SMC_LAUNCH((k_ancestors2<true, true, true, true>), grid, dim3(SMC_BLOCK), st, f->a);
+        else SMC_LAUNCH((k_ancestors2<true, true>), grid, dim3(SMC_BLOCK), st, f->a);
         return;
     }
-    if (f->two_level) {
-        if (f->two_level_mid && f->a.scheme == SMC_MULTINOMIAL) {
-            // (the island's reduction: a launch of its own, or workgroup 0 of the one-pass spacings kernel)
-            const bool merge = f->sp_merge && !f->a.ut && f->a.sp_tpw && t_known;
-            f->a.sp_epoch = merge ? ++f->sp_epoch : 0ull;
-            if (!merge) launch_reduce2(f, st);
-            if (!f->a.ut) {
-                // production mode: uniform_spacings in two passes over the same draws (tile sums, their
-                // prefixes, the uniforms written once); k_ancestors2 finds its window through the prefixes
-                const dim3 g1(f->a.ntiles1, f->a.n_islands);
-                if (f->a.sp_tpw) {                 // one pass (decoupled look-back): every workgroup resident
-                    const dim3 gw(f->a.sp_nwg + (merge ? 1 : 0), f->a.n_islands);
-                    switch (f->a.sp_tpw) {
-                    case 1: SMC_LAUNCH(k_f_spacing_onepass<1>, gw, dim3(SMC_BLOCK), st, f->a); break;
-                    case 2: SMC_LAUNCH(k_f_spacing_onepass<2>, gw, dim3(SMC_BLOCK), st, f->a); break;
-                    case 4: SMC_LAUNCH(k_f_spacing_onepass<4>, gw, dim3(SMC_BLOCK), st, f->a); break;
-                    default: SMC_LAUNCH(k_f_spacing_onepass<8>, gw, dim3(SMC_BLOCK), st, f->a); break;
-                    }
-                } else {
-                    SMC_LAUNCH(k_f_spacing_sums, g1, dim3(SMC_BLOCK), st, f->a);
-                    SMC_LAUNCH(k_f_spacing_scan, dim3(f->a.n_islands), dim3(SMC_BLOCK), st, f->a);
-                    SMC_LAUNCH(k_f_spacing_write, g1, dim3(SMC_BLOCK), st, f->a);
-                }
-                SMC_LAUNCH((k_ancestors2<true, true, true, true>), grid, dim3(SMC_BLOCK), st, f->a);
-            } else {
-                SMC_LAUNCH((k_ancestors2<true, true>), grid, dim3(SMC_BLOCK), st, f->a);
-            }
-        } else {
-            // closed-form counts: one instantiation per scheme (see k_ancestors2's SCH)
-            if (f->two_level_mid) launch_reduce2(f, st);
+    // closed-form counts: one instantiation per scheme (see k_ancestors2's SCH)
 #ifdef SMC_NO_SCHEME_SPLIT                         /* (A/B builds: tools/build_ablations.sh) */
 #define A2_CASE(MIDV, POW2V, SCHV) SMC_LAUNCH((k_ancestors2<MIDV, false, POW2V>), grid, dim3(SMC_BLOCK), st, f->a)
 #else
 #define A2_CASE(MIDV, POW2V, SCHV) SMC_LAUNCH((k_ancestors2<MIDV, false, POW2V, false, false, SCHV>), grid, dim3(SMC_BLOCK), st, f->a)
 #endif
-            const bool sys = f->a.scheme == SMC_SYSTEMATIC, p2 = f->a.log2N >= 0;
-            if (f->two_level_mid) {
-                if (p2) { if (sys) A2_CASE(true, true, SMC_SYSTEMATIC_); else A2_CASE(true, true, SMC_STRATIFIED_); }
-                else { if (sys) A2_CASE(true, false, SMC_SYSTEMATIC_); else A2_CASE(true, false, SMC_STRATIFIED_); }
-            } else if (!p2 && f->wide_tpw) {
-                // resident grid, any N, systematic: two tiles per workgroup over the runs of tiles f_tile_xcd gives the XCDs
-                const int per_run = (f->a.ntiles + 7) / 8;
-                const dim3 gridw(f->a.xcd_chunks ? 8 * ((per_run + 1) / 2) : (f->a.ntiles + 1) / 2, f->a.n_islands);
-                SMC_LAUNCH((k_ancestors2w<2, SMC_SYSTEMATIC_, false>), gridw, dim3(SMC_BLOCK * 2), st, f->a.info2, f->a.pm, f->a.ps,
-                           f->a.pss, f->a.cq, f->a.N, f->a.ntiles | (f->a.xcd_chunks ? 1 << 30 : 0), f->a);
-            } else if (p2 && f->wide_tpw) {
-                // resident grid, N = 2^k: TPW tiles per workgroup, the partials reduced by its first 4 waves only
-                const dim3 gridw(f->a.ntiles / f->wide_tpw, f->a.n_islands);
-                // (leading arguments: the fields the kernel's first loads are addressed with, preloaded into SGPRs)
+    const bool sys = f->a.scheme == SMC_SYSTEMATIC, p2 = f->a.log2N >= 0;
+    if (f->plan.reduce != REDUCE_NONE) {
+        if (p2) { if (sys) A2_CASE(true, true, SMC_SYSTEMATIC_); else A2_CASE(true, true, SMC_STRATIFIED_); }
+        else { if (sys) A2_CASE(true, false, SMC_SYSTEMATIC_); else A2_CASE(true, false, SMC_STRATIFIED_); }
+    } else if (f->plan.resampler == RS_WIDE) {
+        // (leading arguments: the fields the kernel's first loads are addressed with, preloaded into SGPRs)
 #define W_LEAD f->a.info2, f->a.pm, f->a.ps, f->a.pss, f->a.cq, f->a.N, f->a.ntiles | (f->a.xcd_chunks ? 1 << 30 : 0)
-                if (sys) SMC_LAUNCH((k_ancestors2w<2, SMC_SYSTEMATIC_>), gridw, dim3(SMC_BLOCK * 2), st, W_LEAD, f->a);
-                else SMC_LAUNCH((k_ancestors2w<2, SMC_STRATIFIED_>), gridw, dim3(SMC_BLOCK * 2), st, W_LEAD, f->a);
-            } else {
-                if (p2) { if (sys) A2_CASE(false, true, SMC_SYSTEMATIC_); else A2_CASE(false, true, SMC_STRATIFIED_); }
-                else { if (sys) A2_CASE(false, false, SMC_SYSTEMATIC_); else A2_CASE(false, false, SMC_STRATIFIED_); }
-            }
+        if (!p2) {
+            // any N, systematic: the runs of tiles f_tile_xcd gives the XCDs, two tiles per workgroup
+            const int per_run = (f->a.ntiles + 7) / 8;
+            const dim3 gridw(f->a.xcd_chunks ? 8 * ((per_run + 1) / 2) : (f->a.ntiles + 1) / 2, f->a.n_islands);
+            SMC_LAUNCH((k_ancestors2w<F_WIDE_TPW, SMC_SYSTEMATIC_, false>), gridw, dim3(SMC_BLOCK * 2), st, W_LEAD, f->a);
+        } else {
+            // N = 2^k: the partials reduced by the workgroup's first 4 waves only
+            const dim3 gridw(f->a.ntiles / F_WIDE_TPW, f->a.n_islands);
+            if (sys) SMC_LAUNCH((k_ancestors2w<F_WIDE_TPW, SMC_SYSTEMATIC_>), gridw, dim3(SMC_BLOCK * 2), st, W_LEAD, f->a);
+            else SMC_LAUNCH((k_ancestors2w<F_WIDE_TPW, SMC_STRATIFIED_>), gridw, dim3(SMC_BLOCK * 2), st, W_LEAD, f->a);
+        }
+#undef W_LEAD
+    } else {
+        if (p2) { if (sys) A2_CASE(false, true, SMC_SYSTEMATIC_); else A2_CASE(false, true, SMC_STRATIFIED_); }
+        else { if (sys) A2_CASE(false, false, SMC_SYSTEMATIC_); else A2_CASE(false, false, SMC_STRATIFIED_); }
+    }
 #undef A2_CASE
-        }
-        if (k_prof >= 0 && (k_prof % 3)) (void)hipEventRecord(f->ev[3 * k_prof + 1], st);
-        launch_propagate(f);
-        if (k_prof >= 0) (void)hipEventRecord(f->ev[3 * k_prof + 2], st);
-        if (f->a.mom) {      // device-side Moments: the row of the step just done (K, 1/s) first
-            SMC_LAUNCH(k_flush2, dim3(f->a.n_islands), dim3(SMC_BLOCK), st, f->a);
-            SMC_LAUNCH(k_f_moments_partials, dim3(f->a.nmb, f->a.n_islands), dim3(SMC_BLOCK), st, f->a);
-            SMC_LAUNCH(k_f_moments_final, dim3(f->a.n_islands), dim3(SMC_BLOCK), st, f->a);
-        }
-        return;
-    }
-    const bool fused = f->fused;
-    if (f->sq_flat) {
-        // SQMC of a multivariate filter, or of a univariate one of fewer than two tiles (smc_filter_sqmc.h):
-        // Hilbert order (d = 1: the radix argsort), the step's points, the tapes; the flat step then runs as it
-        // is -- its multinomial search over the sorted uniforms in a.su, its propagate kernel fed from the tape
-        // of ndtri values
-        FArgs& a = f->a;
-        const int d = a.dx;
-        const unsigned nb = (unsigned)((a.N + SMC_BLOCK - 1) / SMC_BLOCK);
-        double* U = (double*)f->sq_ws;
-        double* lws = U + (size_t)a.N * (d + 1);
-        a.zt = f->sq_z;
-        a.zt_ts = 0;
-        for (int i = 0; i < a.n_islands; ++i) {
-            const u64 ctr = f->sq_ctr0 + (u64)t + ((u64)(u32)(a.island_offset + i) << 32);
-            if (t == 0) {
-                (void)smc_sobol_points(f->ctx, f->sq_seed, a.N, d, ctr, 0, U);
-                SMC_LAUNCH(k_sqmv_tapes, dim3(nb), dim3(SMC_BLOCK), st, f->a, i, (const i64*)nullptr, (const double*)U, d,
-                           lws, f->sq_z);
+}
+
+// sq_flat: SQMC of a multivariate filter, or of a univariate one of fewer than two tiles (smc_filter_sqmc.h):
+// Hilbert order (d = 1: the radix argsort), the step's points, the tapes; the flat step then runs as it
+// is -- its multinomial search over the sorted uniforms in a.su, its propagate kernel fed from the tape
+// of ndtri values
+static void sqmc_flat_prologue(smc_filter* f, hipStream_t st, i64 t)
+{
+    FArgs& a = f->a;
+    const int d = a.dx;
+    const unsigned nb = (unsigned)((a.N + SMC_BLOCK - 1) / SMC_BLOCK);
+    double* U = (double*)f->sq_ws;
+    double* lws = U + (size_t)a.N * (d + 1);
+    a.zt = f->sq_z;
+    a.zt_ts = 0;
+    for (int i = 0; i < a.n_islands; ++i) {
+        const u64 ctr = f->sq_ctr0 + (u64)t + ((u64)(u32)(a.island_offset + i) << 32);
+        if (t == 0) {
+            (void)smc_sobol_points(f->ctx, f->sq_seed, a.N, d, ctr, 0, U);
+            SMC_LAUNCH(k_sqmv_tapes, dim3(nb), dim3(SMC_BLOCK), st, f->a, i, (const i64*)nullptr, (const double*)U, d,
+                       lws, f->sq_z);
+        } else {
+            i64* perm = (i64*)f->sq_perm + (size_t)i * a.N;
+            if (d == 1) {                      // hilbert.py:52-54: argsort
+                u64* v0 = nullptr;
+                (void)smc_rs_sort_ws(f->ctx, f_X(a, t - 1) + (size_t)i * a.N, nullptr, a.N, 0, (void*)(lws + a.N), nullptr, &v0, f->sq_plan_zero);
+                f->sq_plan_zero = true;
+                (void)hipMemcpyAsync(perm, v0, (size_t)a.N * 8, hipMemcpyDeviceToDevice, st);
             } else {
-                i64* perm = (i64*)f->sq_perm + (size_t)i * a.N;
-                if (d == 1) {                      // hilbert.py:52-54: argsort
-                    u64* v0 = nullptr;
-                    (void)smc_rs_sort_ws(f->ctx, f_X(a, t - 1) + (size_t)i * a.N, nullptr, a.N, 0, (void*)(lws + a.N), nullptr, &v0, f->sq_plan_zero);
-                    f->sq_plan_zero = true;
-                    (void)hipMemcpyAsync(perm, v0, (size_t)a.N * 8, hipMemcpyDeviceToDevice, st);
-                } else {
-                    (void)smc_hilbert_sort(f->ctx, f_X(a, t - 1) + (size_t)i * a.N * d, a.N, d, (int64_t*)perm, nullptr);
-                }
-                (void)smc_sobol_points(f->ctx, f->sq_seed, a.N, d + 1, ctr, 1, U);
-                SMC_LAUNCH(k_sqmv_tapes, dim3(nb), dim3(SMC_BLOCK), st, f->a, i, (const i64*)perm, (const double*)U, d + 1,
-                           lws, f->sq_z);
-                (void)hipMemcpyAsync(f_lw(a, t - 1) + (size_t)i * a.N, lws, (size_t)a.N * 8, hipMemcpyDeviceToDevice, st);
+                (void)smc_hilbert_sort(f->ctx, f_X(a, t - 1) + (size_t)i * a.N * d, a.N, d, (int64_t*)perm, nullptr);
             }
+            (void)smc_sobol_points(f->ctx, f->sq_seed, a.N, d + 1, ctr, 1, U);
+            SMC_LAUNCH(k_sqmv_tapes, dim3(nb), dim3(SMC_BLOCK), st, f->a, i, (const i64*)perm, (const double*)U, d + 1,
+                       lws, f->sq_z);
+            (void)hipMemcpyAsync(f_lw(a, t - 1) + (size_t)i * a.N, lws, (size_t)a.N * 8, hipMemcpyDeviceToDevice, st);
         }
     }
+}
+
+// STEP_FLAT: [k_prepare, (spacings), k_ancestors] do nothing unless the step resamples (decided on the device by
+// the previous k_propagate)
+static void resample_flat(smc_filter* f, hipStream_t st, i64 t)
+{
+    const dim3 grid(f->a.ntiles, f->a.n_islands);
+    if (f->plan.sq_flat) sqmc_flat_prologue(f, st, t);
     if (f->kind == SMC_MODEL_MVLINGAUSS && f->fk == SMC_FK_APF) {
         // auxiliary weights of step t (core.py:307-313) before its resampling: smc_filter_mv.h
         const dim3 gp(f->a.nparts, f->a.n_islands);
@@ -400,20 +544,33 @@ static void enqueue_step(smc_filter* f, int k_prof, i64 t, bool t_known = true)
         else SMC_LAUNCH((k_mv_aux<32, false>), gp, dim3(SMC_BLOCK), st, f->a, f->a.mvc);
         SMC_LAUNCH(k_mv_aux_restate, dim3(f->a.n_islands), dim3(SMC_BLOCK), st, f->a);
     }
+    const bool fused = f->plan.resampler == RS_FUSED;
     if (!fused) SMC_LAUNCH(k_prepare, grid, dim3(SMC_BLOCK), st, f->a);
-    if (f->a.scheme == SMC_MULTINOMIAL && !f->a.ut && !f->sqmc) {
-        const dim3 g1(f->a.ntiles1, f->a.n_islands);
-        SMC_LAUNCH(k_f_spacing_sums, g1, dim3(SMC_BLOCK), st, f->a);
-        SMC_LAUNCH(k_f_spacing_scan, dim3(f->a.n_islands), dim3(SMC_BLOCK), st, f->a);
-        SMC_LAUNCH(k_f_spacing_write, g1, dim3(SMC_BLOCK), st, f->a);
-    }
+    if (draws_spacings(f)) launch_spacings(f, st, false);
     if (fused && f->a.par >= 0) SMC_LAUNCH((k_ancestors<true, true>), grid, dim3(SMC_BLOCK), st, f->a);
     else if (fused) SMC_LAUNCH((k_ancestors<true, false>), grid, dim3(SMC_BLOCK), st, f->a);
     else SMC_LAUNCH((k_ancestors<false, false>), grid, dim3(SMC_BLOCK), st, f->a);
-    if (f->sq_flat && t > 0)                       // A <- h_order[A] (core.py:344)
+    if (f->plan.sq_flat && t > 0)                  // A <- h_order[A] (core.py:344)
         for (int i = 0; i < f->a.n_islands; ++i)
             SMC_LAUNCH(k_sqmv_compose, dim3((unsigned)((f->a.N + SMC_BLOCK - 1) / SMC_BLOCK)), dim3(SMC_BLOCK), st, f->a, i,
                        (const i64*)f->sq_perm + (size_t)i * f->a.N);
+}
+
+// one time step: the resampling part of the plan's kind, then k_propagate and the moments
+static void enqueue_step(smc_filter* f, int k_prof, i64 t, bool t_known = true)
+{
+    // the host knows the time index of every step it enqueues; inside a replayed graph
+    // only its parity is static (graphs hold an even number of steps and start at even t)
+    f->a.par = f->a.hist ? -1 : (int)(t & 1);
+    f->a.tk = (t_known && !f->plan.no_tk) ? t : -1;
+    hipStream_t st = f->ctx->stream;
+    if (k_prof >= 0) (void)hipEventRecord(f->ev[3 * k_prof], st);
+    switch (f->plan.kind) {
+    case STEP_SQMC: resample_sqmc(f, st, t, t_known); break;
+    case STEP_STRICT: resample_strict(f, st, t_known); break;
+    case STEP_TWO_LEVEL: resample_two_level(f, st, t_known); break;
+    case STEP_FLAT: resample_flat(f, st, t); break;
+    }
     // samples come in three kinds (k mod 3): 0 times the whole step, 1 the interval [start,
     // resampling kernels done], 2 the interval [resampling kernels done, end].  Every event
     // interval carries the same ~4 us of marker processing on MI355X (tools/micro/events.hip),
@@ -422,10 +579,249 @@ static void enqueue_step(smc_filter* f, int k_prof, i64 t, bool t_known = true)
     if (k_prof >= 0 && (k_prof % 3)) (void)hipEventRecord(f->ev[3 * k_prof + 1], st);
     launch_propagate(f);
     if (k_prof >= 0) (void)hipEventRecord(f->ev[3 * k_prof + 2], st);
-    if (f->a.mom) {
+    if (f->a.mom) {      // device-side Moments; two-level record: the row of the step just done (K, 1/s) first
+        if (f->plan.two_level) SMC_LAUNCH(k_flush2, dim3(f->a.n_islands), dim3(SMC_BLOCK), st, f->a);
         SMC_LAUNCH(k_f_moments_partials, dim3(f->a.nmb, f->a.n_islands), dim3(SMC_BLOCK), st, f->a);
         SMC_LAUNCH(k_f_moments_final, dim3(f->a.n_islands), dim3(SMC_BLOCK), st, f->a);
     }
+}
+
+
+// ---- smc_filter_create in stages: validate (in the entry itself: its messages carry its name), shape, plan_step,
+// slab_layout, allocation, fill_filter; nothing is allocated before the layout is known
+
+// what validation works out about a MVLINGAUSS model
+struct MvSetup {
+    int dx = 1, dy = 1, dp = 1;
+    std::vector<double> mvc_host;
+    bool diag = false;
+};
+
+// the shape words of the argument block: sizes, grids, scheme
+static void shape_args(FArgs& a, const smc_model* model, const smc_filter_opts* o, const MvSetup& m)
+{
+    const bool mv = model->kind == SMC_MODEL_MVLINGAUSS;
+    const bool sqmc = (o->flags & SMC_FLAG_SQMC) != 0;
+    memset(&a, 0, sizeof a);
+    a.N = o->N;
+    a.T = o->T;
+    a.n_islands = o->n_islands;
+    a.ntiles = (int)((o->N + F_TILE - 1) / F_TILE);
+    a.ntiles1 = (int)((o->N + 1 + F_TILE - 1) / F_TILE);
+    a.scheme = sqmc ? (int)SMC_MULTINOMIAL : (int)o->scheme;            // (sorted uniforms from a tape)
+    a.rng_mode = o->rng_mode;
+    a.island_offset = o->island_offset;
+    a.ess_thresh = sqmc ? INFINITY : (double)o->N * o->ESSrmin;         // (SQMC always resamples, core.py:340)
+    a.seed = o->seed;
+    a.log2N = -1;
+    for (int k = 0; k < 62; ++k)
+        if (((i64)1 << k) == o->N) a.log2N = k;
+    {
+        int lg = 0;
+        while (((i64)1 << lg) < o->N + 2) ++lg;
+        a.spacing_scale = ldexp(1.0, 57 - lg < 21 ? 57 - lg : 21);        // (see smc_ops.hip spacing_scale)
+    }
+    a.dx = m.dx; a.dy = m.dy; a.dp = m.dp;
+    a.hist = o->keep_history;                      // 0 / 1 (whole history) / k >= 2 (rolling window)
+    if (a.hist >= 2 && (i64)a.hist >= a.T) a.hist = 1;       // a window as long as the run: all of it
+    a.xslot = a.N * a.n_islands * m.dx;
+    a.lslot = a.N * a.n_islands;
+    // MV: a workgroup stages the step's matrices in LDS once and then walks
+    // mv_chunks chunks of 256 particles (2 workgroups per CU when N allows)
+    a.mv_chunks = 1;
+    a.mv_diag = (mv && m.diag && !(o->flags & SMC_PATH_MV_DENSE)) ? 1 : 0;
+    if (mv) {
+        // 8 by default, halved until the grid has at least 512 workgroups (element-wise form: 2 workgroups per CU) or
+        // 1024 (dense form: 3 per CU fit); SMC_PATH_MV_CHUNKS(1|2|4|8) (tests) is taken as given, so that the
+        // multi-chunk prefetch loop is audited at small N too
+        const int forced = (o->flags >> 20) & 15;
+        if (forced == 1 || forced == 2 || forced == 4 || forced == 8) a.mv_chunks = forced;
+        else {
+            const i64 min_grid = a.mv_diag ? 512 : 1024;
+            a.mv_chunks = 8;
+            while (a.mv_chunks > 1 && a.N / (SMC_BLOCK * a.mv_chunks) < min_grid) a.mv_chunks >>= 1;
+        }
+    }
+    const i64 per_wg = mv ? (i64)SMC_BLOCK * a.mv_chunks : (i64)SMC_BLOCK * F_OPT;
+    a.nparts = (int)((o->N + per_wg - 1) / per_wg);
+    a.ncq = (i64)a.ntiles * F_TILE;
+    a.nmb = (int)((o->N + F_MOM_CHUNK - 1) / F_MOM_CHUNK);
+    a.exact_counts = (o->flags & SMC_PATH_EXACT_COUNTS) ? 1 : 0;
+    a.tk = -1;
+    // streaming stores pay while a launch is short (its end-of-kernel write-back shows): C2 +8 %;
+    // on the large grids they cost 2 % (C5)
+    a.nt = ((i64)a.ntiles * a.n_islands <= F_DIRECT_PREFIX_MAX && !mv) ? 15 : 0;
+    // (bits: 1 X, 2 lw, 4 the tile CDF, 8 A.  Measured at C2, r12f: any mask that streams lw -- written every step, read
+    //  only on the steps that do not resample -- is as fast as streaming everything, 17.63 us; none: 19.31.  With
+    //  consecutive tiles per XCD, r12w: 15: 17.4, X plain 17.5, X and the tile CDF plain 18.0, lw only 18.3)
+}
+
+// Offsets of every device array in the slab.  The order and the sizes are part of the saved-state format
+// (smc_filter_save_state / load_state / clone go by slab_bytes): do not reorder.
+struct SlabLayout {
+    size_t X, lw, A, Q, Qpre, pm, ps, pss, summ, params, y, aux, mvc, cnt, spart, info, info2, cq, tq, p2, hcnt, hlist, su, E,
+        sst, sdec, tmp, strict_ws, eta, sq_z, sq_perm, sq_ws, mom, mpart, trace, bytes;
+};
+
+static SlabLayout slab_layout(const FArgs& a, const StepPlan& p, const smc_model* model, const smc_filter_opts* o, size_t mvc_words)
+{
+    const bool mv = model->kind == SMC_MODEL_MVLINGAUSS;
+    const size_t M = (size_t)a.n_islands, N = (size_t)a.N, T = (size_t)a.T, dx = (size_t)a.dx;
+    const bool need_su = a.scheme == SMC_MULTINOMIAL;
+    const size_t nslots = a.hist == 1 ? T : (a.hist >= 2 ? (size_t)a.hist : 2);
+    SlabLayout L;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { size_t o0 = off; off = smc_align_up(off + bytes, 256); return o0; };
+    // (+ one tile of padding each: the ragged last tile's loads are unconditional, k_propagate<RAGGED = 1>)
+    L.X = carve(nslots * M * N * dx * 8 + F_TILE * dx * 8);
+    L.lw = carve(nslots * M * N * 8 + F_TILE * 8);
+    L.A = carve(((a.hist ? nslots : 1) * M * N + F_TILE) * 4);
+    L.Q = carve(M * a.ntiles * 8);
+    L.Qpre = carve(M * a.ntiles * 8);
+    L.pm = carve(M * a.nparts * 8);
+    L.ps = carve(M * a.nparts * 8);
+    L.pss = carve(M * a.nparts * 8);
+    L.summ = carve(M * (T + 1) * SUMM_STRIDE * 8);
+    L.params = carve(M * PARAM_STRIDE * 8);
+    L.y = carve(T * a.dy * 8);
+    L.aux = carve(T * 8);
+    L.mvc = carve(mvc_words * 8 + 8);
+    L.cnt = carve(M * 2 * F_CNT_WORDS * sizeof(unsigned));
+    L.spart = carve(M * 96 * 8);
+    L.info = carve(M * INFO_STRIDE * 8);
+    L.info2 = carve(M * INFO_STRIDE * 8);
+    L.cq = carve(p.two_level ? M * (size_t)a.ncq * 8 : 8);
+    L.tq = carve(p.two_level ? M * a.ntiles * 8 : 8);
+    L.p2 = carve(p.apf2 ? 3 * M * a.nparts * 8 : 8);
+    L.hcnt = carve(p.heavy_list ? M * 2 * sizeof(unsigned) : 8);
+    L.hlist = carve(p.heavy_list ? M * 2 * F_HMAX * 3 * 8 : 8);
+    L.su = carve(need_su ? M * N * 8 + 16 : 8);
+    L.E = carve(need_su ? M * (a.ntiles1 + 1) * 8 : 8);
+    L.sst = carve(p.sp_tpw ? M * p.sp_nwg * 8 : 8);
+    L.sdec = carve(M * 8);
+    L.tmp = carve(N * dx * 8);
+    L.strict_ws = carve(p.strict() ? 2 * M * N * 8 + sqx_scratch_bytes((i64)N, (int)M) + M * a.ntiles * 8 + 64 : 8);
+    L.eta = carve(mv && model->fk == SMC_FK_APF ? 2 * M * N * 8 : 8);
+    L.sq_z = carve(p.sqmc() ? M * N * dx * 8 : 8);
+    L.sq_perm = carve(p.sqmc() && (M > 1 || p.sq_flat) ? M * N * 8 : 8);
+    // (two-level: the sort's workspace; flat: the step's points (N, d + 1), a row of sorted log-weights and -- d = 1
+    // -- the sort's workspace behind them)
+    L.sq_ws = carve(!p.sqmc() ? 8 : p.sq_flat ? (N * (dx + 1) + N) * 8 + (mv ? 0 : smc_rs_ws_bytes((i64)N))
+                                               : smc_rs_ws_bytes((i64)N));
+    L.mom = carve(o->moments ? M * T * 2 * dx * 8 : 8);
+    L.mpart = carve(o->moments ? M * a.nmb * dx * 3 * 8 : 8);
+    L.trace = carve(M * (size_t)(2 * a.ntiles + 8) * 8 * 8 + (size_t)(2 * a.ntiles + 16) * 8 * 8);
+    L.bytes = off;
+    return L;
+}
+
+// points the argument block into the slab, zeroes what the kernels expect zero and uploads the model and the data
+static int fill_filter(smc_filter* f, const SlabLayout& L, const smc_model* model, const smc_filter_opts* o, const double* y_host,
+                       const MvSetup& m)
+{
+    smc_ctx* ctx = f->ctx;
+    hipStream_t st = ctx->stream;
+    FArgs& a = f->a;
+    const StepPlan& p = f->plan;
+    const bool mv = f->kind == SMC_MODEL_MVLINGAUSS;
+    const size_t M = (size_t)a.n_islands, N = (size_t)a.N, T = (size_t)a.T;
+    char* base = (char*)f->slab;
+    a.X = (double*)(base + L.X);
+    a.lw = (double*)(base + L.lw);
+    a.A = (u32*)(base + L.A);
+    a.Q = (u64*)(base + L.Q);
+    a.Qpre = (u64*)(base + L.Qpre);
+    a.pm = (double*)(base + L.pm); a.ps = (double*)(base + L.ps); a.pss = (double*)(base + L.pss);
+    a.summ = (double*)(base + L.summ);
+    double* dpar = (double*)(base + L.params);
+    double* dy = (double*)(base + L.y);
+    a.params = dpar;
+    a.y = dy;
+    a.cnt = (unsigned*)(base + L.cnt);
+    a.cq = (u64*)(base + L.cq);
+    a.tq = (u64*)(base + L.tq);
+    a.spart = (double*)(base + L.spart);
+    a.info = (double*)(base + L.info);
+    a.info2 = (double*)(base + L.info2);
+    if (p.heavy_list) {
+        a.hcnt = (unsigned*)(base + L.hcnt);
+        a.hlist = (i64*)(base + L.hlist);
+        SMC_HIP_CHECK(hipMemsetAsync(a.hcnt, 0, M * 2 * sizeof(unsigned), st));
+    }
+    if (p.apf2) {
+        a.pm2 = (double*)(base + L.p2);
+        a.ps2 = a.pm2 + M * a.nparts;
+        a.pss2 = a.ps2 + M * a.nparts;
+    }
+    a.su = (double*)(base + L.su);
+    a.E = (u64*)(base + L.E);
+    a.sst = (u64*)(base + L.sst);
+    if (a.sp_tpw) SMC_HIP_CHECK(hipMemsetAsync(a.sst, 0, M * a.sp_nwg * 8, st));
+    a.sdec = (u64*)(base + L.sdec);
+    SMC_HIP_CHECK(hipMemsetAsync(a.sdec, 0, M * 8, st));
+    f->tmp = (double*)(base + L.tmp);
+    f->strict_ws = (double*)(base + L.strict_ws);
+    if (p.strict())        // (the counters of smc_seqx.h: zero once, re-armed by its passes)
+        sqx_zero_counters(st, (void*)(f->strict_ws + 2 * M * N), (i64)N, (int)M);
+    if (mv && f->fk == SMC_FK_APF) {
+        a.eta = (double*)(base + L.eta);
+        a.lwsv = a.eta + M * N;
+    }
+    if (p.sqmc()) {
+        f->sq_z = (double*)(base + L.sq_z);
+        f->sq_perm = (u64*)(base + L.sq_perm);
+        f->sq_ws = base + L.sq_ws;
+    }
+    {
+        auto it = ctx->pinned.find(M * 8);
+        if (it != ctx->pinned.end() && !it->second.empty()) {
+            f->ll_stage = (double*)it->second.back();
+            it->second.pop_back();
+        } else if (hipHostMalloc((void**)&f->ll_stage, M * 8, hipHostMallocMapped) != hipSuccess) {
+            f->ll_stage = nullptr;
+        }
+    }
+    (void)hipGetLastError();
+    if (o->moments) {
+        a.mom = (double*)(base + L.mom);
+        a.mpart = (double*)(base + L.mpart);
+    }
+    a.trace = (u64*)(base + L.trace);
+    SMC_HIP_CHECK(hipMemsetAsync(a.summ, 0, M * (T + 1) * SUMM_STRIDE * 8, st));
+    SMC_HIP_CHECK(hipMemsetAsync(a.cnt, 0, M * 2 * F_CNT_WORDS * sizeof(unsigned), st));
+    SMC_HIP_CHECK(hipMemsetAsync(a.Q, 0, M * a.ntiles * 8, st));
+    {   // step record of t = 0: {t, rs_flag, y_0, m, 1/s}
+        std::vector<double> h(M * INFO_STRIDE, 0.0);
+        for (size_t i = 0; i < M; ++i) {
+            h[i * INFO_STRIDE + 2] = y_host[0];
+            h[i * INFO_STRIDE + 5] = model->aux_host ? model->aux_host[0] : 0.0;
+        }
+        SMC_HIP_CHECK(hipMemcpyAsync(a.info, h.data(), h.size() * 8, hipMemcpyHostToDevice, st));
+        SMC_HIP_CHECK(hipMemsetAsync(a.info2, 0, M * INFO_STRIDE * 8, st));
+        SMC_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    SMC_HIP_CHECK(hipMemsetAsync(a.A, 0, (M * N + F_TILE) * 4, st));     // (+ the padding tile: valid indices)
+    std::vector<double> par_host(M * PARAM_STRIDE, 0.0);
+    if (!mv) {       // the host's rows + the correctly rounded reciprocals smc_div_c works with
+        for (size_t i = 0; i < M; ++i)
+            for (int k = 0; k < PARAM_HOST; ++k) {
+                const double v = model->params_host[i * PARAM_HOST + k];
+                par_host[i * PARAM_STRIDE + k] = v;
+                const double av = v < 0 ? -v : v;
+                par_host[i * PARAM_STRIDE + PARAM_HOST + k] = (av > 1e-20 && av < 1e20) ? 1.0 / v : 0.0;
+            }
+        SMC_HIP_CHECK(hipMemcpyAsync(dpar, par_host.data(), M * PARAM_STRIDE * 8, hipMemcpyHostToDevice, st));
+    }
+    a.mvc = (const double*)(base + L.mvc);
+    if (mv)
+        SMC_HIP_CHECK(hipMemcpyAsync((void*)a.mvc, m.mvc_host.data(), m.mvc_host.size() * 8, hipMemcpyHostToDevice, st));
+    SMC_HIP_CHECK(hipMemcpyAsync(dy, y_host, T * a.dy * 8, hipMemcpyHostToDevice, st));
+    if (model->aux_host) {
+        a.aux = (const double*)(base + L.aux);
+        SMC_HIP_CHECK(hipMemcpyAsync((void*)a.aux, model->aux_host, T * 8, hipMemcpyHostToDevice, st));
+    }
+    SMC_HIP_CHECK(hipStreamSynchronize(st));
+    return SMC_OK;
 }
 
 extern "C" {
@@ -436,6 +832,7 @@ static void flush_rows(smc_filter* f);
 int smc_filter_create(smc_ctx* ctx, const smc_model* model, const smc_filter_opts* o,
                       const double* y_host, smc_filter** out)
 {
+    // ---- validate
     SMC_REQUIRE(ctx && model && o && y_host && out, "null argument");
     SMC_REQUIRE(o->N > 0 && o->T > 0 && o->n_islands > 0, "N, T, n_islands must be positive");
     if (o->scheme != SMC_MULTINOMIAL && o->scheme != SMC_STRATIFIED &&
@@ -468,17 +865,15 @@ int smc_filter_create(smc_ctx* ctx, const smc_model* model, const smc_filter_opt
     SMC_REQUIRE(model->kind != SMC_MODEL_DISCRETECOX || model->aux_host,
                 "DISCRETECOX needs aux_host (gammaln(y_t + 1) per step)");
     SMC_REQUIRE(mv || model->params_host, "params_host is required");
-    int dxm = 1, dym = 1, dpm = 1;
-    std::vector<double> mvc_host;
-    bool mv_diag = false;
+    MvSetup m;
     if (mv) {
-        dxm = model->dx; dym = model->dy;
-        SMC_REQUIRE(dxm >= 1 && dxm <= 32 && dym >= 1 && dym <= dxm,
+        m.dx = model->dx; m.dy = model->dy;
+        SMC_REQUIRE(m.dx >= 1 && m.dx <= 32 && m.dy >= 1 && m.dy <= m.dx,
                     "MVLINGAUSS needs 1 <= dy <= dx <= 32");
         SMC_REQUIRE(model->F_host && model->G_host && model->covX_host && model->covY_host &&
                         model->mu0_host && model->cov0_host, "MVLINGAUSS matrices are required");
-        dpm = dxm <= 16 ? 16 : 32;              // padded to whole 16x16 MFMA blocks
-        if (!mv_build_constants(model, model->fk, dpm, o->T, y_host, mvc_host, &mv_diag)) {
+        m.dp = m.dx <= 16 ? 16 : 32;            // padded to whole 16x16 MFMA blocks
+        if (!mv_build_constants(model, model->fk, m.dp, o->T, y_host, m.mvc_host, &m.diag)) {
             // same failure as MvNormal.__init__ (distributions.py:935-940)
             smc_set_error("MvNormal: argument cov must be a (d, d) pos. definite matrix");
             return SMC_ERR_INVALID;
@@ -486,386 +881,62 @@ int smc_filter_create(smc_ctx* ctx, const smc_model* model, const smc_filter_opt
     }
     SMC_REQUIRE(o->N < ((i64)1 << 32), "N must be below 2^32");
     SMC_HIP_CHECK(hipSetDevice(ctx->device));
-
-    smc_filter* f = new smc_filter();
-    f->ctx = ctx;
-    f->kind = model->kind;
-    f->fk = model->fk;
-    f->t_host = 0;
-    f->use_graph = o->use_graph != 0;
-    f->gexec[0] = f->gexec[1] = f->gexec[2] = nullptr;
-    f->graph_failed = false;
-    f->prof = false;
-    f->prof_n = 0;
-    f->perm_t = -1;
-    f->lwth = f->th = f->th_ess = nullptr;
-    f->th_buf = nullptr;
-    f->th_ess_min = 0.0;
-    f->th_comm = nullptr;
-    f->th_n = 0;
-    f->th_send = f->th_recv = nullptr;
-    f->mv_collapsed = mv && model->fk == SMC_FK_GUIDED && (o->flags & SMC_FLAG_COLLAPSED_PROPOSAL);
-    f->strict = (o->flags & SMC_FLAG_STRICT_ANCESTORS) != 0;
-    f->strict_literal = (o->flags & SMC_PATH_STRICT_LITERAL) != 0;
-    f->no_small = (o->flags & SMC_PATH_NO_SMALL) != 0;
-    f->strict_ws = nullptr;
-    f->sqmc = (o->flags & SMC_FLAG_SQMC) != 0;
-    f->sq_flat = false;
-    f->sq_gather = (o->flags & SMC_PATH_SQ_GATHER) != 0;
-    f->sq_seed = o->seed;
-    f->sq_ctr0 = 1;
-    f->sq_z = nullptr;
-    f->sq_perm = nullptr;
-    f->sq_ws = nullptr;
-    if (f->sqmc) {
+    const bool strict = (o->flags & SMC_FLAG_STRICT_ANCESTORS) != 0;
+    if (o->flags & SMC_FLAG_SQMC) {
         // core.py:339-349 as a fused loop.  Univariate Normal kernels (Gamma = ppf), N = 2^k >= 2 tiles: the
         // two-level step (the sorted Sobol' order in closed form).  MVLINGAUSS (2 <= d <= 9: d + 1 Sobol'
         // coordinates) and univariate filters of N = 2^k < 2 tiles: the flat step behind the Hilbert sort / the
         // argsort, N >= 32, no history slots (the sorted weights take the slot).
         bool pow2 = false;
         for (int k = 5; k <= 30; ++k) pow2 = pow2 || (((i64)1 << k) == o->N);
-        f->sq_flat = mv || o->N < 2 * F_TILE;
+        const bool flat = sqmc_on_flat_step(model, o);
         const bool fk_ok = model->fk == SMC_FK_BOOTSTRAP || model->fk == SMC_FK_GUIDED;
-        const bool mv_ok = !f->sq_flat || ((!mv || (model->dx >= 2 && model->dx <= 9)) && !o->keep_history && !o->moments &&
-                                           !(o->flags & SMC_FLAG_COLLAPSED_PROPOSAL));
-        if (!fk_ok || !pow2 || !mv_ok || f->strict || o->rng_mode != SMC_RNG_PHILOX || (f->sq_flat && o->use_graph) ||
+        const bool mv_ok = !flat || ((!mv || (model->dx >= 2 && model->dx <= 9)) && !o->keep_history && !o->moments &&
+                                     !(o->flags & SMC_FLAG_COLLAPSED_PROPOSAL));
+        if (!fk_ok || !pow2 || !mv_ok || strict || o->rng_mode != SMC_RNG_PHILOX || (flat && o->use_graph) ||
             (o->flags & (SMC_PATH_FLAT_CDF | SMC_PATH_FORCE_UNFUSED))) {
             smc_set_error("SMC_FLAG_SQMC: Bootstrap / Guided filters, N = 2^k with 5 <= k <= 30, Philox mode; MVLINGAUSS "
                           "(2 <= d <= 9) and univariate models with k <= 10: eager launches, no history slots, no moments");
-            delete f;
             return SMC_ERR_INVALID;
         }
     }
-    const int scheme = f->sqmc ? (int)SMC_MULTINOMIAL : (int)o->scheme;     // (sorted uniforms from a tape)
-    if (f->strict && (mv || f_is_apf(model->fk) || o->N >= ((i64)1 << 32))) {
+    if (strict && (mv || f_is_apf(model->fk) || o->N >= ((i64)1 << 32))) {
         smc_set_error("SMC_FLAG_STRICT_ANCESTORS: univariate Bootstrap / Guided filters");
-        delete f;
         return SMC_ERR_INVALID;
     }
-    FArgs& a = f->a;
-    memset(&a, 0, sizeof a);
-    a.N = o->N;
-    a.T = o->T;
-    a.n_islands = o->n_islands;
-    a.ntiles = (int)((o->N + F_TILE - 1) / F_TILE);
-    a.ntiles1 = (int)((o->N + 1 + F_TILE - 1) / F_TILE);
-    a.scheme = scheme;
-    a.rng_mode = o->rng_mode;
-    a.island_offset = o->island_offset;
-    a.ess_thresh = f->sqmc ? INFINITY : (double)o->N * o->ESSrmin;     // (SQMC always resamples, core.py:340)
-    a.seed = o->seed;
-    a.log2N = -1;
-    for (int k = 0; k < 62; ++k)
-        if (((i64)1 << k) == o->N) a.log2N = k;
-    {
-        int lg = 0;
-        while (((i64)1 << lg) < o->N + 2) ++lg;
-        a.spacing_scale = ldexp(1.0, 57 - lg < 21 ? 57 - lg : 21);        // (see smc_ops.hip spacing_scale)
-    }
-    const size_t M = (size_t)o->n_islands, N = (size_t)o->N, T = (size_t)o->T;
-    const bool need_su = (scheme == SMC_MULTINOMIAL);
-    // carve one slab
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o0 = off; off = smc_align_up(off + bytes, 256); return o0; };
-    a.dx = dxm; a.dy = dym; a.dp = dpm;
     SMC_REQUIRE(o->keep_history >= 0, "keep_history must be 0, 1 or a window length >= 2");
-    a.hist = o->keep_history;                      // 0 / 1 (whole history) / k >= 2 (rolling window)
-    if (a.hist >= 2 && (size_t)a.hist >= T) a.hist = 1;      // a window as long as the run: all of it
-    const size_t nslots = a.hist == 1 ? T : (a.hist >= 2 ? (size_t)a.hist : 2);
-    a.xslot = (i64)(M * N * dxm);
-    a.lslot = (i64)(M * N);
-    // (+ one tile of padding each: the ragged last tile's loads are unconditional, k_propagate<RAGGED = 1>)
-    const size_t oX0 = carve(nslots * M * N * dxm * 8 + F_TILE * dxm * 8);
-    const size_t oL0 = carve(nslots * M * N * 8 + F_TILE * 8);
-    const size_t nA = (a.hist ? nslots : 1) * M * N + F_TILE;
-    const size_t oA = carve(nA * 4);
-    // (published tile totals pay off only while every workgroup of the launch is resident)
-    f->fused = (i64)a.ntiles * (i64)M <= F_DIRECT_PREFIX_MAX;
-    if (o->flags & SMC_PATH_FORCE_UNFUSED) f->fused = false;  // tests: the k_prepare path at any size
-    const size_t oQ = carve(M * a.ntiles * 8);
-    const size_t oQpre = carve(M * a.ntiles * 8);
-    // MV: a workgroup stages the step's matrices in LDS once and then walks
-    // mv_chunks chunks of 256 particles (2 workgroups per CU when N allows)
-    a.mv_chunks = 1;
-    a.mv_diag = (mv && mv_diag && !(o->flags & SMC_PATH_MV_DENSE)) ? 1 : 0;
-    if (mv) {
-        // 8 by default, halved until the grid has at least 512 workgroups (element-wise form: 2 workgroups per CU) or
-        // 1024 (dense form: 3 per CU fit); SMC_PATH_MV_CHUNKS(1|2|4|8) (tests) is taken as given, so that the
-        // multi-chunk prefetch loop is audited at small N too
-        const int forced = (o->flags >> 20) & 15;
-        if (forced == 1 || forced == 2 || forced == 4 || forced == 8) a.mv_chunks = forced;
-        else {
-            const i64 min_grid = a.mv_diag ? 512 : 1024;
-            a.mv_chunks = 8;
-            while (a.mv_chunks > 1 && (i64)N / (SMC_BLOCK * a.mv_chunks) < min_grid) a.mv_chunks >>= 1;
-        }
+
+    // ---- shape, plan, layout: host arithmetic only
+    smc_filter* f = new smc_filter();
+    f->ctx = ctx;
+    f->kind = model->kind;
+    f->fk = model->fk;
+    f->use_graph = o->use_graph != 0;
+    f->sq_seed = o->seed;
+    shape_args(f->a, model, o, m);
+    int rc = plan_step(ctx, model, o, f->a, &f->plan);
+    if (rc == SMC_OK) {
+        // (the plan's words the kernels read)
+        f->a.kform = f->plan.two_level ? 1 : 0;
+        f->a.strict_e = (f->plan.strict() && f->plan.strict_form == STRICT_TWO_LEVEL) ? 1 : 0;
+        f->a.xcd_chunks = f->plan.xcd_chunks ? 1 : 0;
+        f->a.sp_tpw = f->plan.sp_tpw;
+        f->a.sp_nwg = f->plan.sp_nwg;
+        const SlabLayout L = slab_layout(f->a, f->plan, model, o, m.mvc_host.size());
+        // ---- allocate, fill
+        // the slab comes from the context's pool (smc_malloc: blocks recycled by exact size, ordered on
+        // the context's one stream): a PMMH chain or the PMCMC moves of SMC^2 create and destroy a filter
+        // of the same shape per proposal, and hipMalloc / hipFree of tens of MB cost milliseconds each
+        f->slab_bytes = L.bytes;
+        rc = smc_malloc(ctx, L.bytes, &f->slab) == SMC_OK ? SMC_OK : SMC_ERR_NOMEM;
+        if (rc == SMC_OK) rc = fill_filter(f, L, model, o, y_host, m);
     }
-    const i64 per_wg = mv ? (i64)SMC_BLOCK * a.mv_chunks : (i64)SMC_BLOCK * F_OPT;
-    a.nparts = (int)((o->N + per_wg - 1) / per_wg);
-    const size_t oPm = carve(M * a.nparts * 8), oPs = carve(M * a.nparts * 8),
-                 oPss = carve(M * a.nparts * 8);
-    const size_t oSum = carve(M * (T + 1) * SUMM_STRIDE * 8);
-    const size_t oPar = carve(M * PARAM_STRIDE * 8);
-    const size_t oY = carve(T * dym * 8);
-    const size_t oAux = carve(T * 8);
-    const size_t oMvc = carve(mvc_host.size() * 8 + 8);
-    const size_t oCtl = carve(M * 2 * F_CNT_WORDS * sizeof(unsigned));
-    const size_t oSpart = carve(M * 96 * 8);
-    const size_t oInfo = carve(M * INFO_STRIDE * 8);
-    const size_t oInfo2 = carve(M * INFO_STRIDE * 8);
-    // two-level CDF: closed-form offspring counts (N = 2^k, systematic / stratified), at most
-    // 1024 tiles per island (4 partials per thread), at least 2 (below, the one-workgroup filter)
-    // (multinomial: the counts are searches over the sorted uniforms -- the tape's, or the exponential
-    //  spacings drawn between k_reduce2, which decides the step, and k_ancestors2)
-    // (any N >= 2 tiles: N = 2^k counts in closed form with integers, other N with the general counts)
-    f->two_level = !mv && o->N <= ((int64_t)1 << 30) && a.ntiles >= 2 &&
-                   !(o->flags & (SMC_PATH_FLAT_CDF | SMC_PATH_FORCE_UNFUSED));
-    // every workgroup reduces the partials itself while the launch is resident and an island has
-    // at most 1024 tiles (4 per thread); otherwise one workgroup per island does it first
-    const bool apf2 = !mv && f_is_apf(model->fk) && o->N > F_TILE;      // APF on the two-level step: k_reduce2
-    if (apf2 && !f->two_level) {                                      // forms its two reductions
-        smc_set_error("the auxiliary particle filter beyond N = 1024 runs on the two-level step only");
+    if (rc != SMC_OK) {        // the one failure exit: whatever exists by now
+        if (f->slab) (void)smc_free(ctx, f->slab);
+        if (f->ll_stage) (void)hipHostFree(f->ll_stage);
         delete f;
-        return SMC_ERR_INVALID;
+        return rc;
     }
-    f->two_level_mid = f->two_level && (!f->fused || a.ntiles > 1024 || (o->flags & SMC_PATH_TWO_LEVEL_MID) ||
-                                        scheme == SMC_MULTINOMIAL || apf2);
-    // resident grids of N = 2^k: 2 tiles per workgroup (smc_filter_wide.h; C2, same box: 17.6 us per step, 4 tiles 18.3,
-    // one tile -- k_ancestors2 -- 18.1: profiles/r12d); SMC_PATH_NO_WIDE keeps the one-tile kernel testable at these sizes
-    f->wide_tpw = 0;
-    f->reduce_narrow = (o->flags & SMC_PATH_NO_WIDE) != 0;
-    if (f->two_level && !f->two_level_mid && a.log2N >= 0 && !(o->flags & SMC_PATH_NO_WIDE) && !f->strict && !f->sqmc) {
-        f->wide_tpw = (a.ntiles % 2) == 0 ? 2 : 0;
-    }
-    // ... and of any other N under the systematic scheme (k_ancestors2w<2, .., POW2 = false>: the general counts, any
-    // number of tiles -- the last workgroup of a run may hold one tile)
-    if (f->two_level && !f->two_level_mid && a.log2N < 0 && scheme == SMC_SYSTEMATIC && a.ntiles >= 2 &&
-        !(o->flags & SMC_PATH_NO_WIDE) && !f->strict && !f->sqmc)
-        f->wide_tpw = 2;
-    // consecutive tiles on one XCD (f_tile_xcd): any number of tiles with one tile per resampling workgroup; with
-    // k_ancestors2w whole multiples of 8 x (its tiles per workgroup) -- else the wide kernel keeps its own XCD-strided map
-    a.xcd_chunks = (f->two_level && !mv && !f->strict && !f->sqmc && !(o->flags & SMC_PATH_NO_XCD_CHUNKS) && a.ntiles >= 16 &&
-                    (!f->wide_tpw || a.log2N < 0 || a.ntiles % (8 * f->wide_tpw) == 0)) ? 1 : 0;
-    // (measured and kept out, round 4: the reduction MERGED into the resampling launch on grids beyond 2048 workgroups --
-    //  (a) every workgroup of k_ancestors2w reducing: C5 99.2 us per step (2 tiles per workgroup) / 117.2 (4) against 92.9
-    //  behind k_reduce2 (r12h); (b) workgroup 0 of k_ancestors2 reducing, the others waiting for its word with their
-    //  loads in flight and reading (G_b, Q_b) past their L2: C3 60.7 against 57.6 us, C5 159 against 99 -- a dependent
-    //  global round trip in every workgroup costs more than the launch it saves (r12j))
-    // (SQMC: k_ancestors2 counts in SORTED positions; a heavy parent's blocks would be filled with that index)
-    const bool heavy_list = !mv && !f->strict && !f->sqmc && !(o->flags & SMC_PATH_NO_HEAVY);
-    // (history slots are written step by step: the lanes beyond N of a slot would read indices nobody
-    //  initialised -- every access tests its index there as well)
-    a.kform = f->two_level ? 1 : 0;
-    a.strict_e = (f->strict && f->two_level && !f->strict_literal) ? 1 : 0;
-    f->ragged = (f->two_level && (o->N % F_TILE) != 0) ? (((o->N & 1) || a.hist) ? 2 : 1) : 0;
-    a.ncq = (i64)a.ntiles * F_TILE;
-    const size_t oCq = carve(f->two_level ? M * (size_t)a.ncq * 8 : 8);
-    const size_t oTq = carve(f->two_level ? M * a.ntiles * 8 : 8);
-    const size_t oP2 = carve(apf2 ? 3 * M * a.nparts * 8 : 8);
-    const size_t oHcnt = carve(heavy_list ? M * 2 * sizeof(unsigned) : 8);
-    const size_t oHlist = carve(heavy_list ? M * 2 * F_HMAX * 3 * 8 : 8);
-    const size_t oSu = carve(need_su ? M * N * 8 + 16 : 8);
-    const size_t oE = carve(need_su ? M * (a.ntiles1 + 1) * 8 : 8);
-    // one-pass uniform_spacings (two-level step, Philox draws): 1, 2, 4 or 8 tiles of draws per workgroup,
-    // the fewest that keep the whole launch resident (<= 1024 workgroups: half of what the chip holds);
-    // more islands than that: the three-pass form
-    a.sp_tpw = a.sp_nwg = 0;
-    bool merge_fits = false;
-    if (need_su && f->two_level && !(f->strict && f->strict_literal) && !f->sqmc && !(o->flags & SMC_PATH_SPACING_3PASS))
-        for (int tpw = 1; tpw <= 8 && !a.sp_tpw; tpw *= 2) {
-            const int forced_tpw = (o->flags >> 25) & 15;          // SMC_PATH_SP_TPW (A/B: workgroups wait for
-            if (forced_tpw && tpw != forced_tpw) continue;         //  lower-numbered ones only, dispatch is in order)
-            const i64 nwg = (a.ntiles + tpw - 1) / tpw;
-            int per_cu = 0;                        // workgroups of this instantiation a CU holds at once
-#ifdef SMC_EMULATE
-            per_cu = 4;
-            (void)per_cu;
-#else
-            const void* fn = tpw == 1 ? (const void*)k_f_spacing_onepass<1> : tpw == 2 ? (const void*)k_f_spacing_onepass<2>
-                           : tpw == 4 ? (const void*)k_f_spacing_onepass<4> : (const void*)k_f_spacing_onepass<8>;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, SMC_BLOCK, 0) != hipSuccess) per_cu = 0;
-            (void)hipGetLastError();
-#endif
-            // (a margin of one workgroup per CU: the occupancy API is optimistic near register-file edges)
-#ifdef SMC_EMULATE
-            const i64 cap = 1024;                  // (workgroups run one after the other, in order)
-#else
-            const i64 cap = (i64)(per_cu > 1 ? per_cu - 1 : 0) * ctx->n_cu;
-#endif
-            if ((nwg * (i64)M <= cap && nwg * (i64)M <= 1024) || (forced_tpw && nwg <= 1024)) {
-                a.sp_tpw = tpw;
-                a.sp_nwg = (int)nwg;
-                // one workgroup more per island when the reduction rides along (see sp_merge): it is the first
-                // of the launch and waits for nobody, the others wait for lower-numbered ones only -- dispatch is
-                // in order, so the margin kept above is not needed for it, the chip's nominal capacity is
-#ifdef SMC_EMULATE
-                merge_fits = true;
-#else
-                merge_fits = (nwg + 1) * (i64)M <= (i64)per_cu * ctx->n_cu || forced_tpw;
-#endif
-            }
-        }
-    const size_t oSst = carve(a.sp_tpw ? M * a.sp_nwg * 8 : 8);
-    const size_t oSdec = carve(M * 8);
-    f->sp_epoch = 0;
-    f->flush_pending = false;
-    // (inside a replayed graph the argument block -- the epoch with it -- is frozen: separate launches there)
-    f->sp_merge = a.sp_tpw && merge_fits && !o->use_graph && !(o->flags & SMC_PATH_SPLIT_REDUCE);
-    f->sq_plan_zero = false;
-    const size_t oTmp = carve(N * dxm * 8);
-    const size_t oStrict = carve(f->strict ? 2 * M * N * 8 + sqx_scratch_bytes((i64)N, (int)M) + M * a.ntiles * 8 + 64 : 8);
-    if (f->sqmc && !f->sq_flat && !f->two_level) {
-        smc_set_error("SMC_FLAG_SQMC needs the two-level step");
-        delete f;
-        return SMC_ERR_INVALID;
-    }
-    const bool apf_mv = mv && model->fk == SMC_FK_APF;
-    const size_t oEta = carve(apf_mv ? 2 * M * N * 8 : 8);
-    const size_t oSqZ = carve(f->sqmc ? M * N * dxm * 8 : 8);
-    const size_t oSqPerm = carve(f->sqmc && (M > 1 || f->sq_flat) ? M * N * 8 : 8);
-    // (two-level: the sort's workspace; flat: the step's points (N, d + 1), a row of sorted log-weights and -- d = 1
-    // -- the sort's workspace behind them)
-    const size_t oSqWs = carve(!f->sqmc ? 8 : f->sq_flat ? (N * (dxm + 1) + N) * 8 + (mv ? 0 : smc_rs_ws_bytes((i64)N))
-                                                          : smc_rs_ws_bytes((i64)N));
-    a.nmb = (int)((o->N + F_MOM_CHUNK - 1) / F_MOM_CHUNK);
-    const size_t oMom = carve(o->moments ? M * T * 2 * dxm * 8 : 8);
-    const size_t oMpart = carve(o->moments ? M * a.nmb * dxm * 3 * 8 : 8);
-    const size_t oTrace = carve(M * (size_t)(2 * a.ntiles + 8) * 8 * 8 + (size_t)(2 * a.ntiles + 16) * 8 * 8);
-    // the slab comes from the context's pool (smc_malloc: blocks recycled by exact size, ordered on
-    // the context's one stream): a PMMH chain or the PMCMC moves of SMC^2 create and destroy a filter
-    // of the same shape per proposal, and hipMalloc / hipFree of tens of MB cost milliseconds each
-    void* slab = nullptr;
-    if (smc_malloc(ctx, off, &slab) != SMC_OK) {
-        delete f;
-        return SMC_ERR_NOMEM;
-    }
-    f->slab = slab;
-    f->slab_bytes = off;
-    // (from here on a failing HIP call must not leak the slab and the struct)
-#define F_CREATE_CHECK(expr)                                                                   \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) {                                                                \
-            smc_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__,     \
-                          __LINE__);                                                           \
-            (void)smc_free(ctx, slab);                                                         \
-            if (f->ll_stage) (void)hipHostFree(f->ll_stage);                                   \
-            delete f;                                                                          \
-            return SMC_ERR_HIP;                                                                \
-        }                                                                                      \
-    } while (0)
-    char* base = (char*)slab;
-    a.X = (double*)(base + oX0);
-    a.lw = (double*)(base + oL0);
-    a.A = (u32*)(base + oA);
-    a.Q = (u64*)(base + oQ);
-    a.Qpre = (u64*)(base + oQpre);
-    a.pm = (double*)(base + oPm); a.ps = (double*)(base + oPs); a.pss = (double*)(base + oPss);
-    a.summ = (double*)(base + oSum);
-    double* dpar = (double*)(base + oPar);
-    double* dy = (double*)(base + oY);
-    a.params = dpar;
-    a.y = dy;
-    a.cnt = (unsigned*)(base + oCtl);
-    a.cq = (u64*)(base + oCq);
-    a.tq = (u64*)(base + oTq);
-    a.spart = (double*)(base + oSpart);
-    a.info = (double*)(base + oInfo);
-    a.info2 = (double*)(base + oInfo2);
-    if (heavy_list) {
-        a.hcnt = (unsigned*)(base + oHcnt);
-        a.hlist = (i64*)(base + oHlist);
-        F_CREATE_CHECK(hipMemsetAsync(a.hcnt, 0, M * 2 * sizeof(unsigned), ctx->stream));
-    }
-    a.exact_counts = (o->flags & SMC_PATH_EXACT_COUNTS) ? 1 : 0;
-    f->no_tk = (o->flags & SMC_PATH_NO_TK) != 0;
-    a.tk = -1;
-    // streaming stores pay while a launch is short (its end-of-kernel write-back shows): C2 +8 %;
-    // on the large grids they cost 2 % (C5)
-    a.nt = ((i64)a.ntiles * (i64)M <= F_DIRECT_PREFIX_MAX && !mv) ? 15 : 0;
-    // (bits: 1 X, 2 lw, 4 the tile CDF, 8 A.  Measured at C2, r12f: any mask that streams lw -- written every step, read
-    //  only on the steps that do not resample -- is as fast as streaming everything, 17.63 us; none: 19.31.  With
-    //  consecutive tiles per XCD, r12w: 15: 17.4, X plain 17.5, X and the tile CDF plain 18.0, lw only 18.3)
-    a.pm2 = a.ps2 = a.pss2 = nullptr;
-    if (apf2) {
-        a.pm2 = (double*)(base + oP2);
-        a.ps2 = a.pm2 + M * a.nparts;
-        a.pss2 = a.ps2 + M * a.nparts;
-    }
-    a.su = (double*)(base + oSu);
-    a.E = (u64*)(base + oE);
-    a.sst = (u64*)(base + oSst);
-    if (a.sp_tpw) F_CREATE_CHECK(hipMemsetAsync(a.sst, 0, M * a.sp_nwg * 8, ctx->stream));
-    a.sdec = (u64*)(base + oSdec);
-    F_CREATE_CHECK(hipMemsetAsync(a.sdec, 0, M * 8, ctx->stream));
-    f->tmp = (double*)(base + oTmp);
-    f->strict_ws = (double*)(base + oStrict);
-    if (f->strict)         // (the counters of smc_seqx.h: zero once, re-armed by its passes)
-        sqx_zero_counters(ctx->stream, (void*)(f->strict_ws + 2 * M * N), (i64)N, (int)M);
-    if (apf_mv) {
-        a.eta = (double*)(base + oEta);
-        a.lwsv = a.eta + M * N;
-    }
-    if (f->sqmc) {
-        f->sq_z = (double*)(base + oSqZ);
-        f->sq_perm = (u64*)(base + oSqPerm);
-        f->sq_ws = base + oSqWs;
-    }
-    f->ll_stage = nullptr;
-    {
-        auto it = ctx->pinned.find(M * 8);
-        if (it != ctx->pinned.end() && !it->second.empty()) {
-            f->ll_stage = (double*)it->second.back();
-            it->second.pop_back();
-        } else if (hipHostMalloc((void**)&f->ll_stage, M * 8, hipHostMallocMapped) != hipSuccess) {
-            f->ll_stage = nullptr;
-        }
-    }
-    (void)hipGetLastError();
-    if (o->moments) {
-        a.mom = (double*)(base + oMom);
-        a.mpart = (double*)(base + oMpart);
-    }
-    a.trace = (u64*)(base + oTrace);
-    hipStream_t st = ctx->stream;
-    F_CREATE_CHECK(hipMemsetAsync(a.summ, 0, M * (T + 1) * SUMM_STRIDE * 8, st));
-    F_CREATE_CHECK(hipMemsetAsync(a.cnt, 0, M * 2 * F_CNT_WORDS * sizeof(unsigned), st));
-    F_CREATE_CHECK(hipMemsetAsync(a.Q, 0, M * a.ntiles * 8, st));
-    {   // step record of t = 0: {t, rs_flag, y_0, m, 1/s}
-        std::vector<double> h(M * INFO_STRIDE, 0.0);
-        for (size_t i = 0; i < M; ++i) {
-            h[i * INFO_STRIDE + 2] = y_host[0];
-            h[i * INFO_STRIDE + 5] = model->aux_host ? model->aux_host[0] : 0.0;
-        }
-        F_CREATE_CHECK(hipMemcpyAsync(a.info, h.data(), h.size() * 8, hipMemcpyHostToDevice, st));
-        F_CREATE_CHECK(hipMemsetAsync(a.info2, 0, M * INFO_STRIDE * 8, st));
-        F_CREATE_CHECK(hipStreamSynchronize(st));
-    }
-    F_CREATE_CHECK(hipMemsetAsync(a.A, 0, (M * N + F_TILE) * 4, st));     // (+ the padding tile: valid indices)
-    std::vector<double> par_host(M * PARAM_STRIDE, 0.0);
-    if (!mv) {       // the host's rows + the correctly rounded reciprocals smc_div_c works with
-        for (size_t i = 0; i < M; ++i)
-            for (int k = 0; k < PARAM_HOST; ++k) {
-                const double v = model->params_host[i * PARAM_HOST + k];
-                par_host[i * PARAM_STRIDE + k] = v;
-                const double av = v < 0 ? -v : v;
-                par_host[i * PARAM_STRIDE + PARAM_HOST + k] = (av > 1e-20 && av < 1e20) ? 1.0 / v : 0.0;
-            }
-        F_CREATE_CHECK(hipMemcpyAsync(dpar, par_host.data(), M * PARAM_STRIDE * 8,
-                                     hipMemcpyHostToDevice, st));
-    }
-    a.mvc = (const double*)(base + oMvc);
-    if (mv)
-        F_CREATE_CHECK(hipMemcpyAsync((void*)a.mvc, mvc_host.data(), mvc_host.size() * 8,
-                                     hipMemcpyHostToDevice, st));
-    F_CREATE_CHECK(hipMemcpyAsync(dy, y_host, T * dym * 8, hipMemcpyHostToDevice, st));
-    if (model->aux_host) {
-        a.aux = (const double*)(base + oAux);
-        F_CREATE_CHECK(hipMemcpyAsync((void*)a.aux, model->aux_host, T * 8, hipMemcpyHostToDevice, st));
-    }
-    F_CREATE_CHECK(hipStreamSynchronize(st));
-    F_CREATE_CHECK(hipStreamSynchronize(st));
-#undef F_CREATE_CHECK
     *out = f;
     return SMC_OK;
 }
@@ -1007,7 +1078,7 @@ int smc_filter_save_state(smc_filter* f, void* out_host, int64_t nbytes)
     h.magic = F_STATE_MAGIC; h.slab_bytes = f->slab_bytes;
     h.N = f->a.N; h.T = f->a.T; h.t_host = f->t_host; h.perm_t = f->perm_t;
     h.n_islands = f->a.n_islands; h.scheme = f->a.scheme; h.kind = f->kind; h.fk = f->fk; h.hist = f->a.hist; h.dx = f->a.dx;
-    h.flags_strict = f->strict ? 1 : 0; h.flags_sqmc = f->sqmc ? 1 : 0;
+    h.flags_strict = f->plan.strict() ? 1 : 0; h.flags_sqmc = f->plan.sqmc() ? 1 : 0;
     h.seed = f->a.seed; h.sp_epoch = f->sp_epoch; h.sq_seed = f->sq_seed; h.sq_ctr0 = f->sq_ctr0;
     h.flush_pending = f->flush_pending ? 1 : 0; h.island_offset = f->a.island_offset;
     memcpy(out_host, &h, sizeof h);
@@ -1025,8 +1096,8 @@ int smc_filter_load_state(smc_filter* f, const void* in_host, int64_t nbytes)
     SMC_REQUIRE(h.magic == F_STATE_MAGIC, "not a filter state (magic)");
     SMC_REQUIRE(h.slab_bytes == f->slab_bytes && nbytes == (int64_t)(sizeof h + h.slab_bytes) && h.N == f->a.N && h.T == f->a.T &&
                     h.n_islands == f->a.n_islands && h.scheme == f->a.scheme && h.kind == f->kind && h.fk == f->fk &&
-                    h.hist == f->a.hist && h.dx == f->a.dx && h.flags_strict == (f->strict ? 1 : 0) &&
-                    h.flags_sqmc == (f->sqmc ? 1 : 0),
+                    h.hist == f->a.hist && h.dx == f->a.dx && h.flags_strict == (f->plan.strict() ? 1 : 0) &&
+                    h.flags_sqmc == (f->plan.sqmc() ? 1 : 0),
                 "the state belongs to a filter of another shape (model, N, T, islands, scheme, history or flags differ)");
     SMC_HIP_CHECK(hipSetDevice(f->ctx->device));
     SMC_HIP_CHECK(hipMemcpyAsync(f->slab, (const char*)in_host + sizeof h, f->slab_bytes, hipMemcpyHostToDevice, f->ctx->stream));
@@ -1057,7 +1128,7 @@ int smc_filter_reseed(smc_filter* f, uint64_t seed)
 int smc_filter_sqmc_points(smc_filter* f, uint64_t point_seed, uint64_t counter0)
 {
     SMC_REQUIRE(f, "null filter");
-    SMC_REQUIRE(f->sqmc, "the filter was not created with SMC_FLAG_SQMC");
+    SMC_REQUIRE(f->plan.sqmc(), "the filter was not created with SMC_FLAG_SQMC");
     SMC_REQUIRE(f->t_host == 0, "the point stream must be chosen before the first step");
     f->sq_seed = point_seed;
     f->sq_ctr0 = counter0;
@@ -1067,7 +1138,7 @@ int smc_filter_sqmc_points(smc_filter* f, uint64_t point_seed, uint64_t counter0
 int smc_filter_set_replay(smc_filter* f, const double* z, const double* u)
 {
     SMC_REQUIRE(f, "null filter");
-    SMC_REQUIRE(!f->sqmc, "SMC_FLAG_SQMC filters generate their points on the device");
+    SMC_REQUIRE(!f->plan.sqmc(), "SMC_FLAG_SQMC filters generate their points on the device");
     SMC_REQUIRE(f->t_host == 0, "replay tapes must be set before the first step");
     SMC_REQUIRE(z && u, "both tapes are required");
     f->a.zt = z;
@@ -1082,8 +1153,7 @@ int smc_filter_set_replay(smc_filter* f, const double* z, const double* u)
 // requested steps in a single launch (smc_filter_small.h)
 static bool small_filter_ok(const smc_filter* f)
 {
-    return f->a.N <= F_TILE && f->kind != SMC_MODEL_MVLINGAUSS && !f->a.mom && !f->prof && !f->strict &&
-           !(f->a.scheme == SMC_MULTINOMIAL && !f->a.ut) && !f->no_small && !f->sqmc;
+    return f->plan.small && !f->prof && !philox_multinomial(f->a);
 }
 
 static void launch_small(smc_filter* f, int nsteps)
@@ -1149,18 +1219,18 @@ int smc_filter_step(smc_filter* f, int64_t nsteps)
             if (small) launch_small(f, 1);
             else {
                 enqueue_step(f, -1, f->t_host + k);
-                if (f->two_level) SMC_LAUNCH(k_flush2, dim3(f->a.n_islands), dim3(SMC_BLOCK), st, f->a);
+                if (f->plan.two_level) SMC_LAUNCH(k_flush2, dim3(f->a.n_islands), dim3(SMC_BLOCK), st, f->a);
             }
             if (f->th_comm) {
                 // sharded population: my filters' increments -> all ranks' (ncclAllGather on this stream, no
                 // host round trip) -> the replicated theta level, the same arithmetic on every rank
                 SMC_LAUNCH(k_theta_pack, dim3(1), dim3(SMC_BLOCK), st, f->a, (const double*)f->th, f->th_send,
-                           f->two_level ? 1 : 0);
+                           f->plan.two_level ? 1 : 0);
                 const int rc = smc_comm_allgather_f64_async(f->th_comm, f->th_send, f->a.n_islands, f->th_recv);
                 if (rc) return rc;
             }
             SMC_LAUNCH(k_theta_update, dim3(1), dim3(SMC_BLOCK), st, f->a, f->lwth, f->th, f->th_ess,
-                       f->th_ess_min, f->two_level ? 1 : 0, (const double*)(f->th_comm ? f->th_recv : nullptr),
+                       f->th_ess_min, f->plan.two_level ? 1 : 0, (const double*)(f->th_comm ? f->th_recv : nullptr),
                        f->th_comm ? f->th_n : f->a.n_islands);
         }
         SMC_LAUNCH_CHECK();
@@ -1180,7 +1250,7 @@ int smc_filter_step(smc_filter* f, int64_t nsteps)
     static const int F_GRAPH_SIZES[3] = {24, 8, 2};
     if (f->use_graph && !f->prof && !f->graph_failed && todo >= 2) {
         // graphs start at even t (SQMC: at even t >= 2 -- step 0 has no sort, the captured sequence always does)
-        while (done < todo && (((f->t_host + done) & 1) || (f->sqmc && f->t_host + done < 2))) {
+        while (done < todo && (((f->t_host + done) & 1) || (f->plan.sqmc() && f->t_host + done < 2))) {
             enqueue_step(f, -1, f->t_host + done);
             ++done;
         }
@@ -1211,7 +1281,7 @@ int smc_filter_step(smc_filter* f, int64_t nsteps)
         if (f->prof && f->prof_n < PROF_MAX) kp = f->prof_n++;
         enqueue_step(f, kp, f->t_host + done);
     }
-    if (f->two_level && todo > 0) f->flush_pending = true;      // summary row of the last step: flush_rows, on demand
+    if (f->plan.two_level && todo > 0) f->flush_pending = true;      // summary row of the last step: flush_rows, on demand
     SMC_LAUNCH_CHECK();
     f->t_host += todo;
     return SMC_OK;
@@ -1343,7 +1413,7 @@ static int filter_fetch(smc_filter* f, int field, i64 s, int island, void* out_h
     }
     case SMC_FIELD_W: {
         const double* row = f->a.summ + ((size_t)island * (f->a.T + 1) + (t - 1)) * SUMM_STRIDE;
-        SMC_LAUNCH(k_f_write_W, dim3(nb), dim3(SMC_BLOCK), st, lw, N, row, f->tmp, f->two_level ? 1 : 0);
+        SMC_LAUNCH(k_f_write_W, dim3(nb), dim3(SMC_BLOCK), st, lw, N, row, f->tmp, f->plan.two_level ? 1 : 0);
         src = f->tmp;
         break;
     }
@@ -1393,8 +1463,8 @@ int smc_filter_set_state(smc_filter* f, int island, const double* X_host, const 
         SMC_HIP_CHECK(hipMemcpyAsync(f_lw(f->a, ts) + (size_t)island * N, lw_host, (size_t)N * 8,
                                      hipMemcpyHostToDevice, st));
         SMC_LAUNCH(k_f_partials, dim3(f->a.nparts, f->a.n_islands), dim3(SMC_BLOCK), st, f->a, ts,
-                   f->two_level ? 1 : 0);
-        if (f->two_level) SMC_LAUNCH(k_flush2, dim3(f->a.n_islands), dim3(SMC_BLOCK), st, f->a);
+                   f->plan.two_level ? 1 : 0);
+        if (f->plan.two_level) SMC_LAUNCH(k_flush2, dim3(f->a.n_islands), dim3(SMC_BLOCK), st, f->a);
         else SMC_LAUNCH(k_f_restate, dim3(f->a.n_islands), dim3(SMC_BLOCK), st, f->a, ts);
     }
     SMC_LAUNCH_CHECK();
@@ -1415,7 +1485,7 @@ static int island_arrays(smc_filter* f, i64 t, IslandArray* out)
     out[n++] = {a.summ, (T + 1) * SUMM_STRIDE};
     out[n++] = {a.info, INFO_STRIDE};
     if (f->kind != SMC_MODEL_MVLINGAUSS) out[n++] = {(void*)a.params, PARAM_STRIDE};
-    if (f->two_level) {
+    if (f->plan.two_level) {
         out[n++] = {a.pm, a.nparts};
         out[n++] = {a.ps, a.nparts};
         out[n++] = {a.pss, a.nparts};
@@ -1500,7 +1570,7 @@ int smc_filter_copy_islands(smc_filter* dst, smc_filter* src, const unsigned cha
     }
     SMC_REQUIRE(a.N == b.N && a.T == b.T && a.n_islands == b.n_islands && a.dx == b.dx &&
                     dst->kind == src->kind && dst->fk == src->fk && dst->t_host == src->t_host &&
-                    dst->two_level == src->two_level,
+                    dst->plan.two_level == src->plan.two_level,
                 "the two filters must have the same shape, model kind and time index");
     const i64 t = dst->t_host;
     if (t == 0) return SMC_OK;
@@ -1599,7 +1669,7 @@ int smc_filter_fast_forward(smc_filter* f, int64_t t)
     SMC_REQUIRE(f, "null filter");
     SMC_REQUIRE(f->t_host == 0, "smc_filter_fast_forward: the filter has already stepped");
     SMC_REQUIRE(t >= 0 && t <= f->a.T, "smc_filter_fast_forward: t must be in [0, T]");
-    SMC_REQUIRE(!f->a.hist && !f->sqmc && !f->lwth, "smc_filter_fast_forward: no history slots, SQMC or theta level");
+    SMC_REQUIRE(!f->a.hist && !f->plan.sqmc() && !f->lwth, "smc_filter_fast_forward: no history slots, SQMC or theta level");
     f->t_host = t;
     f->perm_t = t;
     return SMC_OK;
@@ -1850,7 +1920,7 @@ int smc_filter_info(smc_filter* f, double* bytes_per_particle_step, int* kernels
 {
     SMC_REQUIRE(f, "null filter");
     if (bytes_per_particle_step) *bytes_per_particle_step = 16.0 * f->a.dx + 40.0;
-    if (kernels_per_step) *kernels_per_step = (f->a.scheme == SMC_MULTINOMIAL && !f->a.ut) ? 5 : 3;
+    if (kernels_per_step) *kernels_per_step = philox_multinomial(f->a) ? 5 : 3;
     return SMC_OK;
 }
 
@@ -1869,7 +1939,7 @@ int smc_filter_profile(smc_filter* f, int enable)
 int smc_filter_strict_stats(smc_filter* f, int32_t island, int64_t* exact_path, int64_t* exceptions)
 {
     SMC_REQUIRE(f && exact_path && exceptions, "null argument");
-    SMC_REQUIRE(f->strict && !f->strict_literal, "not a strict_ancestors filter");
+    SMC_REQUIRE(f->plan.strict() && f->plan.strict_form != STRICT_LITERAL, "not a strict_ancestors filter");
     SMC_REQUIRE(island >= 0 && island < f->a.n_islands, "island out of range");
     const SqxArgs q = sqx_carve((void*)(f->strict_ws + 2 * (size_t)f->a.n_islands * f->a.N), f->a.N, f->a.n_islands);
     unsigned long long c[2] = {0ull, 0ull};
@@ -1883,40 +1953,36 @@ int smc_filter_strict_stats(smc_filter* f, int32_t island, int64_t* exact_path, 
 int smc_filter_describe(smc_filter* f, char* out, size_t n)
 {
     SMC_REQUIRE(f && out && n > 0, "null argument");
+    const StepPlan& p = f->plan;
     const bool mv = f->kind == SMC_MODEL_MVLINGAUSS;
+    const bool draws = draws_spacings(f);
+    const std::string reduce = p.reduce == REDUCE_WIDE ? "k_reduce2w+" : p.reduce == REDUCE_NARROW ? "k_reduce2+" : "";
+    const std::string mv_chunks = " [mv_chunks=" + std::to_string(f->a.mv_chunks) + "]";
+    const char* ancestors = p.resampler == RS_FUSED ? "k_ancestors<fused>" : p.resampler == RS_PREPARE ? "k_prepare+k_ancestors"
+                            : p.resampler == RS_WIDE ? "k_ancestors2w" : "k_ancestors2";
+    // (the strict kinds do not list their spacings and moments launches, SQMC on the flat step not its moments: kept as
+    //  they are, tests and the benchmark's model compare these strings)
     std::string s;
     if (small_filter_ok(f)) s = "k_filter_small";
-    else if (f->sq_flat) {
-        s = std::string(mv ? "smc_hilbert_sort" : "k_rs_sort") + "+k_sobol+k_sqmv_tapes+" + (f->fused ? "k_ancestors<fused>" : "k_prepare+k_ancestors") +
-            "+k_sqmv_compose+" + (mv ? "k_propagate_mv [mv_chunks=" + std::to_string(f->a.mv_chunks) + "]" : std::string("k_propagate"));
-    } else if (f->sqmc) {
-        s = "k_rs_sort+k_sq_permute+k_reduce2+k_ancestors2+k_propagate";
+    else if (p.sq_flat)
+        s = std::string(mv ? "smc_hilbert_sort" : "k_rs_sort") + "+k_sobol+k_sqmv_tapes+" + ancestors + "+k_sqmv_compose+" +
+            (mv ? "k_propagate_mv" + mv_chunks : std::string("k_propagate"));
+    else if (p.kind == STEP_SQMC) {
+        s = "k_rs_sort+k_sq_permute+" + reduce + "k_ancestors2+k_propagate";
         if (f->a.mom) s += "+k_f_moments_partials+k_f_moments_final";
-    } else if (f->strict) {
-        if (f->strict_literal) s = std::string(f->two_level ? "k_reduce2+" : "") + "k_strict_W+k_strict_cdf+k_strict_search_S+k_propagate";
-        else if (f->two_level) s = std::string(f->two_level_mid ? "k_reduce2+" : "") +
-                                   std::string("k_strict_classify+k_strict_search") + "+k_propagate";
-        else s = "k_strict_W+k_sqx_classify+k_sqx_fill+k_strict_search_S+k_propagate";
+    } else if (p.kind == STEP_STRICT) {
+        s = reduce + (p.strict_form == STRICT_LITERAL     ? "k_strict_W+k_strict_cdf+k_strict_search_S"
+                      : p.strict_form == STRICT_TWO_LEVEL ? "k_strict_classify+k_strict_search"
+                                                          : "k_strict_W+k_sqx_classify+k_sqx_fill+k_strict_search_S") + "+k_propagate";
     } else {
-        if (f->two_level_mid) s = "k_reduce2+k_ancestors2";
-        else if (f->two_level) s = f->wide_tpw ? "k_ancestors2w" : "k_ancestors2";
-        else if (f->fused) s = "k_ancestors<fused>";
-        else s = "k_prepare+k_ancestors";
-        if (f->a.scheme == SMC_MULTINOMIAL && !f->a.ut)
-            s = (f->a.sp_tpw ? "k_f_spacing_onepass+" : "k_f_spacing_sums+k_f_spacing_scan+k_f_spacing_write+") + s;
-        if (f->sp_merge && f->a.scheme == SMC_MULTINOMIAL && !f->a.ut && f->two_level_mid) {
-            const size_t p = s.find("+k_reduce2");
-            if (p != std::string::npos) s.replace(0, p + 10, "k_f_spacing_onepass<with k_reduce2>");
-        }
+        if (draws && p.spacings == SP_ONEPASS_MERGED) s = "k_f_spacing_onepass<with k_reduce2>+";
+        else s = (!draws ? "" : p.spacings == SP_THREE_PASS ? "k_f_spacing_sums+k_f_spacing_scan+k_f_spacing_write+"
+                                                              : "k_f_spacing_onepass+") + reduce;
+        s += ancestors;
         if (mv && f->fk == SMC_FK_APF) s = "k_mv_aux+k_mv_aux_restate+" + s;
-        s += mv ? (f->mv_collapsed ? "+k_propagate_mv<collapsed>" : "+k_propagate_mv") : "+k_propagate";
-        if (mv) s += " [mv_chunks=" + std::to_string(f->a.mv_chunks) + "]" + (f->a.mv_diag ? " [diagonal factors]" : "");
+        s += mv ? (p.mv_collapsed ? "+k_propagate_mv<collapsed>" : "+k_propagate_mv") : "+k_propagate";
+        if (mv) s += mv_chunks + (f->a.mv_diag ? " [diagonal factors]" : "");
         if (f->a.mom) s += "+k_f_moments_partials+k_f_moments_final";
-    }
-    {   // (islands of 1025 .. 4096 tiles: the reduction's launch is the 1024-thread kernel, launch_reduce2)
-        const int nchunks = (f->a.nparts + 4 * SMC_BLOCK - 1) / (4 * SMC_BLOCK);
-        const size_t p = s.find("k_reduce2+");
-        if (p != std::string::npos && nchunks >= 2 && nchunks <= 4 && !f->a.pm2 && !f->reduce_narrow) s.replace(p, 10, "k_reduce2w+");
     }
     snprintf(out, n, "%s", s.c_str());
     return SMC_OK;

@@ -374,6 +374,7 @@ typedef struct smc_filter_opts {
 #define SMC_PATH_SQ_GATHER        (1 << 29)  /* SMC_FLAG_SQMC: gather the sorted log-weights where they could be recomputed */
 #define SMC_PATH_MV_DENSE         (1 << 3)   /* MVLINGAUSS with diagonal G / covX / covY / cov0: the dense MFMA products all the same (the twin the
                                                element-wise form is checked against, bit for bit; bench.py's c4_dense leg) */
+#define SMC_PATH_EAGER_LW         (1 << 17)  /* every step stores its log-weights: also the resampling steps inside a smc_filter_step call, whose lw nobody reads */
 #define SMC_PATH_SP_TPW(n)        (((n) & 15) << 25)   /* one-pass spacings: n = 1, 2, 4, 8 tiles of draws per workgroup */
 #define SMC_PATH_MV_CHUNKS(n)    (((n) & 15) << 20)   /* k_propagate_mv: n = 1, 2, 4, 8 chunks per workgroup */
 
@@ -401,6 +402,9 @@ int smc_filter_set_replay(smc_filter* f, const double* z, const double* u);
 int smc_filter_step(smc_filter* f, int64_t nsteps);
 int smc_filter_sync(smc_filter* f);
 int smc_filter_t(smc_filter* f, int64_t* t_out);      /* steps enqueued so far */
+/* steps launched so far without the store of their log-weights: resampling steps in the interior of a
+   smc_filter_step call (two-level bootstrap filters; none under SMC_PATH_EAGER_LW).  Synchronises. */
+int smc_filter_lazy_lw_steps(smc_filter* f, int64_t* out);
 /* Per-step summaries (collectors.py:278-295) of steps [0, t):
  * out_host (n_islands, t, 5) = ESS, log_mean_w, loglt, logLt, rs_flag. */
 #define SMC_SUMMARY_COLS 5

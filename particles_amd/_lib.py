@@ -54,7 +54,8 @@ FLAG_SQMC = 4
 PATH_FLAGS = {"SMC_FLAT_CDF": 1 << 8, "SMC_TWO_LEVEL_MID": 1 << 9, "SMC_EXACT_COUNTS": 1 << 10,
               "SMC_FORCE_UNFUSED": 1 << 12, "SMC_NO_SMALL": 1 << 13, "SMC_NO_HEAVY": 1 << 15, "SMC_NO_TK": 1 << 16,
               "SMC_SPACING_3PASS": 1 << 19, "SMC_SPLIT_REDUCE": 1 << 24, "SMC_SQ_GATHER": 1 << 29, "SMC_NO_WIDE": 1 << 30,
-              "SMC_STRICT_LITERAL": 1 << 6, "SMC_NO_XCD_CHUNKS": 1 << 5, "SMC_MV_DENSE": 1 << 3}
+              "SMC_STRICT_LITERAL": 1 << 6, "SMC_NO_XCD_CHUNKS": 1 << 5, "SMC_MV_DENSE": 1 << 3,
+              "SMC_EAGER_LW": 1 << 17}
 
 
 def path_flags():
@@ -133,6 +134,7 @@ SIGNATURES = {
     "smc_filter_step": (c_int, [c_vp, c_i64]),
     "smc_filter_sync": (c_int, [c_vp]),
     "smc_filter_t": (c_int, [c_vp, P(c_i64)]),
+    "smc_filter_lazy_lw_steps": (c_int, [c_vp, P(c_i64)]),
     "smc_filter_summaries": (c_int, [c_vp, P(c_dbl)]),
     "smc_filter_logLt": (c_int, [c_vp, P(c_dbl)]),
     "smc_elementwise": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_dbl, c_i64, c_vp]),

@@ -55,6 +55,15 @@
 //     RS_TILE / RS_WIDE with it.  RS_WIDE (k_ancestors2w) only under STEP_TWO_LEVEL with reduce == REDUCE_NONE: N = 2^k
 //     with an even number of tiles (either closed-form scheme) or any other N under the systematic scheme; SMC_PATH_NO_WIDE
 //     keeps RS_TILE.  The template arguments come from a.log2N (POW2) and a.scheme.
+//   * lazy_lw: on a step that resamples, k_propagate's log-weights are read by nobody unless the NEXT step does not
+//     resample -- and that step can form them again from X (bootstrap move behind a resampling: lw = log p(y | x)).  Where
+//     the plan says so, the steps in the INTERIOR of one smc_filter_step call leave that store out (8 of the 24 bytes per
+//     particle the launch writes); the last step of every call stores, so whoever holds the filter between two calls
+//     sees lw as ever.  Needs STEP_TWO_LEVEL (strict and flat steps read lw when they resample; SQMC sorts them), two
+//     alternating slots (hist == 0: the kernels that take their slots from a.par), no device moments (they read lw of
+//     every step), a bootstrap filter of a model whose observation density reads the new particle only (not SVLEVERAGE;
+//     MVLINGAUSS is never two-level), eager launches (no use_graph) and not SMC_PATH_EAGER_LW (the verification twin:
+//     every step stores).  The theta level's loop and captured steps never ask for it (enqueue_step's `lazy`).
 //   * small: N <= 1024, univariate, no moments: smc_filter_step runs k_filter_small instead of any of the above unless
 //     profiling is on or the draws are Philox multinomial (small_filter_ok); SMC_PATH_NO_SMALL, strict and SQMC never do.
 enum StepKind { STEP_FLAT, STEP_TWO_LEVEL, STEP_STRICT, STEP_SQMC };
@@ -81,6 +90,7 @@ struct StepPlan {
     bool sq_recompute = false;     // STEP_SQMC: sorted weights recomputed from the sorted keys (k_sq_permute<.., true>)
     bool mv_collapsed = false;     // MVLINGAUSS guided: log G = log p(y_t | x_{t-1}) in one product (opts.flags)
     bool no_tk = false;            // SMC_PATH_NO_TK: kernels never start on the host's time index (A/B)
+    bool lazy_lw = false;          // interior steps of a smc_filter_step call may leave a resampling step's lw unwritten
 
     bool strict() const { return kind == STEP_STRICT; }
     bool sqmc() const { return kind == STEP_SQMC || sq_flat; }
@@ -104,6 +114,10 @@ struct smc_filter {
     // SMC_FLAG_SQMC (smc_filter_sqmc.h): the point stream, the tape of ndtri(second coordinate), the
     // sort's workspace and -- more than one island -- the islands' permutations
     u64 sq_seed = 0, sq_ctr0 = 1;
+    // plan.lazy_lw: the time indices enqueued with a.lw_lazy set whose decisions smc_filter_lazy_lw_steps has not looked
+    // up yet, and the count of those it has found resampled (= launched without the lw store)
+    std::vector<i64> lazy_pending;
+    i64 lazy_elided = 0;
     double* sq_z = nullptr;
     u64* sq_perm = nullptr;
     void* sq_ws = nullptr;
@@ -239,6 +253,8 @@ static int plan_step(const smc_ctx* ctx, const smc_model* model, const smc_filte
                      a.n_islands == 1 && a.N > 2048;
     p.mv_collapsed = mv && model->fk == SMC_FK_GUIDED && (flags & SMC_FLAG_COLLAPSED_PROPOSAL);
     p.no_tk = (flags & SMC_PATH_NO_TK) != 0;
+    p.lazy_lw = p.kind == STEP_TWO_LEVEL && a.hist == 0 && !o->moments && !o->use_graph &&
+                model->fk == SMC_FK_BOOTSTRAP && model->kind != SMC_MODEL_SVLEVERAGE && !mv && !(flags & SMC_PATH_EAGER_LW);
     *out = p;
     return SMC_OK;
 }
@@ -557,8 +573,13 @@ static void resample_flat(smc_filter* f, hipStream_t st, i64 t)
 }
 
 // one time step: the resampling part of the plan's kind, then k_propagate and the moments
-static void enqueue_step(smc_filter* f, int k_prof, i64 t, bool t_known = true)
+// lazy: the caller enqueues another step behind this one before it returns to ITS caller (plan.lazy_lw then lets
+// k_propagate leave a resampling step's log-weights unwritten)
+static void enqueue_step(smc_filter* f, int k_prof, i64 t, bool t_known = true, bool lazy = false)
 {
+    f->a.lw_prev_lazy = f->a.lw_lazy;               // (0 behind the last step of a call, a captured step, a theta step)
+    f->a.lw_lazy = (lazy && t_known && f->plan.lazy_lw && !f->lwth) ? 1 : 0;
+    if (f->a.lw_lazy) f->lazy_pending.push_back(t);
     // the host knows the time index of every step it enqueues; inside a replayed graph
     // only its parity is static (graphs hold an even number of steps and start at even t)
     f->a.par = f->a.hist ? -1 : (int)(t & 1);
@@ -1003,6 +1024,8 @@ int smc_filter_clone(smc_filter* src, smc_filter** out)
     f->prof = false;
     f->prof_n = 0;
     f->ev.clear();
+    f->lazy_pending.clear();                                // (counts what THIS filter enqueues)
+    f->lazy_elided = 0;
     f->ll_stage = nullptr;
     f->th_buf = nullptr;
     f->lwth = f->th = f->th_ess = nullptr;
@@ -1100,6 +1123,7 @@ int smc_filter_load_state(smc_filter* f, const void* in_host, int64_t nbytes)
                     h.flags_sqmc == (f->plan.sqmc() ? 1 : 0),
                 "the state belongs to a filter of another shape (model, N, T, islands, scheme, history or flags differ)");
     SMC_HIP_CHECK(hipSetDevice(f->ctx->device));
+    { int64_t n; const int rc = smc_filter_lazy_lw_steps(f, &n); if (rc) return rc; }    // (its rows are about to be replaced)
     SMC_HIP_CHECK(hipMemcpyAsync(f->slab, (const char*)in_host + sizeof h, f->slab_bytes, hipMemcpyHostToDevice, f->ctx->stream));
     SMC_HIP_CHECK(hipStreamSynchronize(f->ctx->stream));
     f->t_host = h.t_host; f->perm_t = h.perm_t;
@@ -1279,11 +1303,34 @@ int smc_filter_step(smc_filter* f, int64_t nsteps)
     for (; done < todo; ++done) {
         int kp = -1;
         if (f->prof && f->prof_n < PROF_MAX) kp = f->prof_n++;
-        enqueue_step(f, kp, f->t_host + done);
+        enqueue_step(f, kp, f->t_host + done, true, done + 1 < todo);
     }
     if (f->plan.two_level && todo > 0) f->flush_pending = true;      // summary row of the last step: flush_rows, on demand
     SMC_LAUNCH_CHECK();
     f->t_host += todo;
+    return SMC_OK;
+}
+
+// How many steps this filter has launched WITHOUT the log-weight store (plan.lazy_lw): the steps enqueued with
+// a.lw_lazy set in which some island resampled -- the host knows the former, the decisions are word 4 of the steps'
+// summary rows (written by the launch that opens the step).  Synchronises.
+int smc_filter_lazy_lw_steps(smc_filter* f, int64_t* out)
+{
+    SMC_REQUIRE(f && out, "null argument");
+    if (!f->lazy_pending.empty()) {
+        SMC_HIP_CHECK(hipSetDevice(f->ctx->device));
+        const i64 T = f->a.T;
+        std::vector<double> h((size_t)f->a.n_islands * (T + 1) * SUMM_STRIDE);
+        SMC_HIP_CHECK(hipMemcpyAsync(h.data(), f->a.summ, h.size() * 8, hipMemcpyDeviceToHost, f->ctx->stream));
+        SMC_HIP_CHECK(hipStreamSynchronize(f->ctx->stream));
+        for (const i64 t : f->lazy_pending) {
+            bool any = false;
+            for (int i = 0; i < f->a.n_islands; ++i) any = any || h[((size_t)i * (T + 1) + t) * SUMM_STRIDE + 4] != 0.0;
+            f->lazy_elided += any ? 1 : 0;
+        }
+        f->lazy_pending.clear();
+    }
+    *out = f->lazy_elided;
     return SMC_OK;
 }
 

@@ -143,6 +143,11 @@ struct FArgs {
     int strict_e;          // SMC_FLAG_STRICT_ANCESTORS on the two-level step: nobody reads the tile's integer CDF, so `cq` holds
                            // every particle's weight on its TILE's scale instead, e_j = p_j 2^(k_j - K_b) (a double): what
                            // k_strict_classify forms W_j from without evaluating an exponential again
+    // log-weights a resampling step would write and nobody would read (StepPlan::lazy_lw; set per launch by enqueue_step)
+    int lw_lazy;           // this launch of k_propagate may leave its lw slot unwritten when the step resamples: a later
+                           // launch of the same smc_filter_step call forms what it needs of it again
+    int lw_prev_lazy;      // the step before was launched so: if it resampled (row t-1 of summ, word 4), its lw slot is
+                           // stale and lw_{t-1} = log p(y_{t-1} | x_{t-1}) is formed again from X_{t-1}
 };
 // Workgroups go round the 8 XCDs (each with its own L2): with tile = workgroup index, neighbouring tiles sit on
 // different XCDs -- but a tile's offspring start in the tile next door as soon as the weights drift, and their parents'
@@ -364,6 +369,19 @@ __device__ __forceinline__ double m_step(const double* p, bool first, double y, 
     inc = (m_norm_logpdf(x, p[0] * xp, p[1], p[16 + 1], p[5]) + m_obs_logpdf<KIND>(p, y, x, xp, first, aux))
           - m_norm_logpdf(x, mu, p[10], p[16 + 10], p[11]);
     return x;
+}
+
+// the log-weight k_propagate leaves behind a bootstrap move that followed a resampling (lw = 0 + inc, NaN -> -inf:
+// resampling.py:220): a function of the step's observation and the new particle alone (SVLEVERAGE excepted: its
+// density reads the parent), through the m_obs_logpdf call m_step makes -- the same operations, hence the same bits,
+// when a later step forms it again from the stored particle (FArgs::lw_prev_lazy)
+template <int KIND>
+__device__ __forceinline__ double m_boot_lw_again(const double* p, double y, double aux, double x)
+{
+    static_assert(KIND != SMC_MODEL_SVLEVERAGE, "needs the parent");
+    double l = m_obs_logpdf<KIND>(p, y, x, 0.0, false, aux);
+    if (l != l) l = -INFINITY;
+    return l;
 }
 
 // W_i as the device defines it: exp(lw_i - m) * (1/s)   (resampling.py:222,225)
@@ -1489,6 +1507,10 @@ k_propagate(const u32* __restrict__ pre_A, double* __restrict__ pre_info, const 
     const double* zt = a.zt ? a.zt + ((i64)t * a.zt_ts + (i64)isl * N) : nullptr;
     const bool first = (t == 0);
     const bool resample = !first && smc_uniform(r1) != 0.0;
+    // log-weights nobody reads (the host's plan sets the two words on these instantiations only): a resampling step's
+    // lw is read by the NEXT step alone, and only if that one does not resample -- it then forms them again
+    constexpr bool LAZY = SPEC && !TAIL && FK == SMC_FK_BOOTSTRAP && KIND != SMC_MODEL_SVLEVERAGE;
+    const bool keep_lw = !(LAZY && a.lw_lazy && resample);
     // ---- is this block of offspring wholly a registered heavy parent's?  Then that parent is
     // everybody's ancestor here and the block's A entries are ours to write
     i64 heavy_parent = -1;
@@ -1515,6 +1537,25 @@ k_propagate(const u32* __restrict__ pre_A, double* __restrict__ pre_info, const 
         // log-weight: requested first, consumed after the normals are generated
         if (resample && !SPEC) {
             load_anc(A);
+        } else if (LAZY && !first && !resample && a.lw_prev_lazy &&
+                   smc_uniform(smc_ldg(a.summ + ((i64)isl * (a.T + 1) + (t - 1)) * SUMM_STRIDE + 4)) != 0.0) {
+            // (rare: step t-1 resampled and left its lw slot as it was -- the same values from X_{t-1}, y_{t-1})
+            if constexpr (LAZY) {
+                if (full) {
+                    smc_ld2g(Xo + own.na, xp[0], xp[1]);
+                    smc_ld2g(Xo + own.nb, xp[2], xp[3]);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < OPT; ++k) {
+                        const i64 n = f_own_idx(own, k);
+                        xp[k] = (n < N) ? smc_ldg(Xo + n) : 0.0;
+                    }
+                }
+                const double y_prev = smc_uniform(smc_ldg(a.y + (t - 1) * a.dy));
+                const double aux_prev = (m_has_aux<KIND>() && a.aux) ? smc_uniform(smc_ldg(a.aux + (t - 1))) : 0.0;
+#pragma unroll
+                for (int k = 0; k < OPT; ++k) lwp[k] = m_boot_lw_again<KIND>(p, y_prev, aux_prev, xp[k]);
+            }
         } else if (!first && !resample) {
             if (full) {
                 smc_ld2g(Xo + own.na, xp[0], xp[1]);
@@ -1587,7 +1628,9 @@ k_propagate(const u32* __restrict__ pre_A, double* __restrict__ pre_info, const 
                 smc_st2g(Xn + own.na, xn[0], xn[1]);
                 smc_st2g(Xn + own.nb, xn[2], xn[3]);
             }
-            if (a.nt & 2) {
+            if (!keep_lw) {
+                // (nothing: 8 B per particle that the next resampling would discard)
+            } else if (a.nt & 2) {
                 smc_st2g_nt(lwn + own.na, lw[0], lw[1]);
                 smc_st2g_nt(lwn + own.nb, lw[2], lw[3]);
             } else {
@@ -1598,7 +1641,7 @@ k_propagate(const u32* __restrict__ pre_A, double* __restrict__ pre_info, const 
 #pragma unroll
             for (int k = 0; k < OPT; ++k) {
                 const i64 n = f_own_idx(own, k);
-                if (n < N) { smc_stg(Xn + n, xn[k]); smc_stg(lwn + n, lw[k]); }
+                if (n < N) { smc_stg(Xn + n, xn[k]); if (keep_lw) smc_stg(lwn + n, lw[k]); }
             }
         }
     }

@@ -492,6 +492,19 @@ int smc_filter_trajectories(smc_filter* f, int island, int64_t* out_host);
 /* keep_history filters: one genealogical line (extract_one_trajectory, smoothing.py:256-269):
  * out_host (t, dx) = X_s[n_s] with n_{t-1} = n_last and n_{s-1} = A_s[n_s]. */
 int smc_filter_one_trajectory(smc_filter* f, int island, int64_t n_last, double* out_host);
+enum smc_backward_method { SMC_BACKWARD_ON2 = 0, SMC_BACKWARD_MCMC = 1 };
+/* keep_history == 1 filters, univariate kinds LINGAUSS / STOCHVOL / GORDON / THETALOGISTIC / DISCRETECOX: M trajectories by
+ * backward sampling over the t steps executed so far (smoothing.py:278-350): SMC_BACKWARD_ON2 is the exact O(N) draw per
+ * trajectory and step (backward_sampling_ON2), SMC_BACKWARD_MCMC `nsteps` independent Metropolis steps with proposals
+ * from W_s (backward_sampling_mcmc).  idx_out_host (t, M) int64; paths_out_host (t, M) fp64 or NULL = X_s[idx[s]].
+ * idx_last_host (M) / u_last_host (M) / u_host ((t-1, M), MCMC: (t-1, nsteps, M) proposals) / u_acc_host (t-1, nsteps, M):
+ * replay tapes or NULL (Philox stream 3, key `seed`, counter (i M + m, s, island, 3); nsteps M < 2^32).  Every index is
+ * the inverse of one uniform in an integer CDF.  Reads the history only: the filter can go on stepping.
+ * SMC_ERR_INVALID: SVLEVERAGE, MVLINGAUSS, SQMC filters, keep_history != 1, M < 1, nsteps < 1, no step executed. */
+int smc_filter_backward_sample(smc_filter* f, int island, int method, int64_t M, int nsteps, uint64_t seed,
+                               const int64_t* idx_last_host, const double* u_last_host,
+                               const double* u_host, const double* u_acc_host,
+                               int64_t* idx_out_host, double* paths_out_host);
 int smc_filter_info(smc_filter* f, double* bytes_per_particle_step,
                     int* kernels_per_step);
 /* Average duration (ms) of the step's two parts -- the propagate kernel ("move") and the

@@ -155,6 +155,18 @@ class ParticleHistory(RollingParticleHistory):
     def __init__(self, fk, qmc):
         self.X, self.A, self.wgts = [], [], []
         self.fk = fk
+        self.qmc = bool(qmc)
+
+    def backward_sampling_ON2(self, M, **kw):
+        """Backward sampling runs on the device-resident history of a fused filter
+        (``DeviceParticleHistory``); a history kept on the host has no sampler."""
+        if self.qmc:
+            raise ValueError("backward sampling: SQMC filters are not supported (backward_sampling_qmc "
+                             "is a different algorithm)")
+        raise NotImplementedError("backward sampling needs the device-resident history of a fused filter")
+
+    def backward_sampling_mcmc(self, M, nsteps=1, **kw):
+        return self.backward_sampling_ON2(M, **kw)
 
 
 class _LazySteps:
@@ -239,6 +251,76 @@ class DeviceParticleHistory:
         _lib.check(_lib.lib().smc_filter_one_trajectory(smc._f, 0, n, out.ctypes.data_as(
             _lib.P(_lib.c_dbl))))
         return [row[0] if d == 1 else row.copy() for row in out]
+
+    def backward_sampling_ON2(self, M, seed=None, island=0, replay=None, return_idx=False):
+        """Exact FFBS (smoothing.py:291-311), on the device: M trajectories, each step of each drawn
+        from ``exp_and_normalise(lw_t + logpt(t + 1, X_t, x_{t+1}))`` -- O(N) work per trajectory
+        and step, one workgroup per trajectory (a trajectory's N particles are not split over
+        workgroups: M = 1 at large N runs on one compute unit).
+
+        Returns the reference's list of T arrays ``paths[t]`` of shape (M,) (scalars for M = 1);
+        with ``return_idx`` also the (T, M) array of particle indices.  The last row holds M iid
+        draws from the final weights in draw order -- the reference's ``rs.multinomial(W, M)``
+        returns them sorted: the same set of trajectories in law, another order.
+
+        seed : Philox key of the draws (stream 3, counter (m, t, island, 3)); None: a fresh one,
+            derived like the filter's default seed.
+        replay : dict of uniforms to use instead: ``idx_last`` (M,) int64 or ``u_last`` (M,) for the
+            last row, ``u`` (T-1, M) for the backward steps.
+        """
+        return self._backward(_lib.BACKWARD_ON2, M, 1, seed, island, replay, return_idx)
+
+    def backward_sampling_mcmc(self, M, nsteps=1, seed=None, island=0, replay=None, return_idx=False):
+        """MCMC backward sampling (smoothing.py:313-350; Dau & Chopin 2022), on the device: each
+        trajectory starts a step from the ancestor of its particle and makes ``nsteps`` independent
+        Metropolis steps whose proposals are iid draws from W_t -- O(nsteps) work per trajectory and
+        step after one O(N) pass that forms the CDF of W_t.  Returns what ``backward_sampling_ON2``
+        returns.  The proposals have the law of the reference's ``multinomial_iid``; its NumPy
+        permutation stream is not reproduced.
+
+        replay : ``idx_last`` / ``u_last`` as for ON2, ``u_prop`` and ``u_acc`` (T-1, nsteps, M).
+        """
+        return self._backward(_lib.BACKWARD_MCMC, M, nsteps, seed, island, replay, return_idx)
+
+    def _backward(self, method, M, nsteps, seed, island, replay, return_idx):
+        smc = self._smc
+        M, nsteps, T = int(M), int(nsteps), smc._n
+        if seed is None:
+            from .core import _default_seed
+            seed = _default_seed()
+        replay = dict(replay or {})
+        shape = (max(T - 1, 0), M) if method == _lib.BACKWARD_ON2 else (max(T - 1, 0), nsteps, M)
+        names = {"idx_last": ((M,), np.int64), "u_last": ((M,), np.float64),
+                 ("u" if method == _lib.BACKWARD_ON2 else "u_prop"): (shape, np.float64)}
+        if method == _lib.BACKWARD_MCMC:
+            names["u_acc"] = (shape, np.float64)
+        unknown = set(replay) - set(names)
+        if unknown:
+            raise ValueError("backward sampling: unknown replay tape(s) %s" % sorted(unknown))
+        tapes = {}
+        for k, (shp, dt) in names.items():
+            if replay.get(k) is None:
+                tapes[k] = None
+                continue
+            a = np.ascontiguousarray(replay[k], dtype=dt)
+            if M >= 1 and nsteps >= 1 and a.shape != shp:
+                raise ValueError("backward sampling: replay[%r] has shape %s, expected %s" % (k, a.shape, shp))
+            tapes[k] = a
+        ptr = lambda a, ct: a.ctypes.data_as(_lib.P(ct)) if a is not None else None
+        idx = np.empty((T, max(M, 0)), dtype=np.int64)
+        paths = np.empty((T, max(M, 0)))
+        try:
+            _lib.check(_lib.lib().smc_filter_backward_sample(
+                smc._f, int(island), method, M, nsteps, int(seed) & (2 ** 64 - 1),
+                ptr(tapes["idx_last"], _lib.c_i64), ptr(tapes["u_last"], _lib.c_dbl),
+                ptr(tapes.get("u", tapes.get("u_prop")), _lib.c_dbl), ptr(tapes.get("u_acc"), _lib.c_dbl),
+                ptr(idx, _lib.c_i64), ptr(paths, _lib.c_dbl)))
+        except ValueError as e:
+            if "model kind" in str(e):
+                raise NotImplementedError(str(e)) from None
+            raise
+        out = [paths[t, 0] if M == 1 else paths[t].copy() for t in range(T)]      # (_output_backward_sampling)
+        return (out, idx) if return_idx else out
 
 
 class DeviceRollingParticleHistory:

@@ -9,6 +9,7 @@
 #include "smc_filter_sqmc.h"
 #include "smc_filter_wide.h"
 #include "smc_filter_strict.h"
+#include "smc_smooth.h"
 
 // ---------------------------------------------------------------------------
 // host side
@@ -1960,6 +1961,108 @@ int smc_filter_one_trajectory(smc_filter* f, int island, int64_t n_last, double*
     if (rc == hipSuccess) rc = hipStreamSynchronize(st);
     (void)hipFree(buf);
     SMC_HIP_CHECK(rc);
+    return SMC_OK;
+}
+
+// Backward sampling over the resident history (smc_smooth.h).  Workspaces come from the context's pool and are used
+// on its stream only; the one synchronisation is the download at the end.
+int smc_filter_backward_sample(smc_filter* f, int island, int method, int64_t M, int nsteps, uint64_t seed,
+                               const int64_t* idx_last_host, const double* u_last_host,
+                               const double* u_host, const double* u_acc_host,
+                               int64_t* idx_out_host, double* paths_out_host)
+{
+    if (f) { (void)hipSetDevice(f->ctx->device); flush_rows(f); }
+    SMC_REQUIRE(f && idx_out_host, "null argument");
+    SMC_REQUIRE(!f->plan.sqmc(), "SQMC filters are not supported (backward_sampling_qmc is a different algorithm)");
+    SMC_REQUIRE(f->kind != SMC_MODEL_SVLEVERAGE, "model kind SVLEVERAGE is not supported: its transition reads y_{t-1}");
+    SMC_REQUIRE(f->kind != SMC_MODEL_MVLINGAUSS, "model kind MVLINGAUSS is not supported: univariate models only");
+    SMC_REQUIRE(f->kind == SMC_MODEL_LINGAUSS || f->kind == SMC_MODEL_STOCHVOL || f->kind == SMC_MODEL_GORDON ||
+                f->kind == SMC_MODEL_THETALOGISTIC || f->kind == SMC_MODEL_DISCRETECOX, "model kind is not supported");
+    SMC_REQUIRE(f->a.hist == 1, "the filter was created without a whole history (keep_history = 1)");
+    SMC_REQUIRE(island >= 0 && island < f->a.n_islands, "island out of range");
+    SMC_REQUIRE(method == SMC_BACKWARD_ON2 || method == SMC_BACKWARD_MCMC, "unknown method");
+    SMC_REQUIRE(M >= 1 && M < ((int64_t)1 << 31), "M must be at least 1 (and below 2^31)");
+    SMC_REQUIRE(nsteps >= 1, "nsteps must be at least 1");
+    const i64 t = f->t_host, N = f->a.N, T = f->a.T;
+    SMC_REQUIRE(t >= 1, "no step has run yet");
+    if (method == SMC_BACKWARD_ON2) nsteps = 1;
+    SMC_REQUIRE((i64)nsteps * M < ((i64)1 << 32), "nsteps * M must stay below 2^32 (Philox counter)");
+    if (idx_last_host)
+        for (i64 m = 0; m < M; ++m) SMC_REQUIRE(idx_last_host[m] >= 0 && idx_last_host[m] < N, "idx_last out of range");
+    hipStream_t st = f->ctx->stream;
+    SmPool pool(f->ctx);
+    const bool mcmc = method == SMC_BACKWARD_MCMC;
+    const bool need_cdf = mcmc || !idx_last_host;
+    const unsigned nch = (unsigned)((N + SM_CHUNK - 1) / SM_CHUNK);
+    i64* idx = nullptr;
+    u64 *cdf = nullptr, *tot = nullptr;
+    double *paths = nullptr, *d_ulast = nullptr, *d_u = nullptr, *d_uacc = nullptr;
+    int rc = pool.get((size_t)t * M, &idx);
+    if (rc == SMC_OK && need_cdf) rc = pool.get((size_t)N, &cdf);
+    if (rc == SMC_OK && need_cdf) rc = pool.get((size_t)nch, &tot);
+    if (rc == SMC_OK && paths_out_host) rc = pool.get((size_t)t * M, &paths);
+    if (rc == SMC_OK && !idx_last_host) rc = pool.upload(u_last_host, (size_t)M, &d_ulast);
+    const size_t per_step = (size_t)nsteps * M;
+    if (rc == SMC_OK) rc = pool.upload(u_host, (size_t)(t - 1) * per_step, &d_u);
+    if (rc == SMC_OK && mcmc) rc = pool.upload(u_acc_host, (size_t)(t - 1) * per_step, &d_uacc);
+    if (rc != SMC_OK) return rc;
+    SMC_HIP_CHECK(hipMemsetAsync(idx, 0, (size_t)t * M * 8, st));          // (every index a kernel reads is in range)
+
+    const double* rows = f->a.summ + (size_t)island * (T + 1) * SUMM_STRIDE;
+    SmArgs s{};
+    s.p = f->a.params + (size_t)island * PARAM_STRIDE;
+    s.N = N; s.M = M;
+    s.seed = seed;
+    s.island = (u32)(f->a.island_offset + island);
+    s.kform = f->plan.two_level ? 1 : 0;
+    s.shift = sm_shift(N);
+    s.nsteps = nsteps;
+    s.cdf = cdf;
+    auto weights_cdf = [&](i64 step) {
+        const double* lw = f_lw(f->a, step) + (size_t)island * N;
+        const double* row = rows + (size_t)step * SUMM_STRIDE;
+        SMC_LAUNCH(k_sm_cdf_totals, dim3(nch), dim3(SMC_BLOCK), st, lw, row, N, s.kform, s.shift, tot);
+        SMC_LAUNCH(k_sm_cdf_scan, dim3(nch), dim3(SMC_BLOCK), st, lw, row, N, s.kform, s.shift, (const u64*)tot, cdf);
+    };
+    // last row: M iid draws from W_{t-1} (smoothing.py:278-281)
+    if (idx_last_host) {
+        SMC_HIP_CHECK(hipMemcpyAsync(idx + (size_t)(t - 1) * M, idx_last_host, (size_t)M * 8, hipMemcpyHostToDevice, st));
+    } else {
+        weights_cdf(t - 1);
+        s.t = (u32)(t - 1);
+        s.u = d_ulast;
+        s.idx_out = idx + (size_t)(t - 1) * M;
+        SMC_LAUNCH(k_sm_draw_last, dim3((unsigned)((M + SMC_BLOCK - 1) / SMC_BLOCK)), dim3(SMC_BLOCK), st, s);
+    }
+    for (i64 b = t - 2; b >= 0; --b) {
+        if (mcmc) weights_cdf(b);
+        s.t = (u32)b;
+        s.Xt = f_X(f->a, b) + (size_t)island * N;
+        s.lwt = f_lw(f->a, b) + (size_t)island * N;
+        s.Xn = f_X(f->a, b + 1) + (size_t)island * N;
+        s.An = f_A(f->a, b + 1) + (size_t)island * N;
+        s.rowt = rows + (size_t)b * SUMM_STRIDE;
+        s.rown = rows + (size_t)(b + 1) * SUMM_STRIDE;
+        s.aux = f->a.aux ? f->a.aux + (b + 1) : nullptr;
+        s.u = d_u ? d_u + (size_t)b * per_step : nullptr;
+        s.u_acc = d_uacc ? d_uacc + (size_t)b * per_step : nullptr;
+        s.idx_next = idx + (size_t)(b + 1) * M;
+        s.idx_out = idx + (size_t)b * M;
+        switch (f->kind) {
+        case SMC_MODEL_LINGAUSS: sm_launch_step<SMC_MODEL_LINGAUSS>(method, st, s); break;
+        case SMC_MODEL_STOCHVOL: sm_launch_step<SMC_MODEL_STOCHVOL>(method, st, s); break;
+        case SMC_MODEL_GORDON: sm_launch_step<SMC_MODEL_GORDON>(method, st, s); break;
+        case SMC_MODEL_THETALOGISTIC: sm_launch_step<SMC_MODEL_THETALOGISTIC>(method, st, s); break;
+        default: sm_launch_step<SMC_MODEL_DISCRETECOX>(method, st, s); break;
+        }
+    }
+    if (paths)
+        SMC_LAUNCH(k_sm_paths, dim3((unsigned)(((size_t)t * M + SMC_BLOCK - 1) / SMC_BLOCK)), dim3(SMC_BLOCK), st, f->a, island,
+                   t, (i64)M, (const i64*)idx, paths);
+    SMC_LAUNCH_CHECK();
+    SMC_HIP_CHECK(hipMemcpyAsync(idx_out_host, idx, (size_t)t * M * 8, hipMemcpyDeviceToHost, st));
+    if (paths) SMC_HIP_CHECK(hipMemcpyAsync(paths_out_host, paths, (size_t)t * M * 8, hipMemcpyDeviceToHost, st));
+    SMC_HIP_CHECK(hipStreamSynchronize(st));
     return SMC_OK;
 }
 

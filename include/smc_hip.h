@@ -492,7 +492,8 @@ int smc_filter_trajectories(smc_filter* f, int island, int64_t* out_host);
 /* keep_history filters: one genealogical line (extract_one_trajectory, smoothing.py:256-269):
  * out_host (t, dx) = X_s[n_s] with n_{t-1} = n_last and n_{s-1} = A_s[n_s]. */
 int smc_filter_one_trajectory(smc_filter* f, int island, int64_t n_last, double* out_host);
-enum smc_backward_method { SMC_BACKWARD_ON2 = 0, SMC_BACKWARD_MCMC = 1 };
+/* (SMC_BACKWARD_REJECT names smc_filter_backward_reject's sampler; smc_filter_backward_sample does not take it) */
+enum smc_backward_method { SMC_BACKWARD_ON2 = 0, SMC_BACKWARD_MCMC = 1, SMC_BACKWARD_REJECT = 2 };
 /* keep_history == 1 filters, univariate kinds LINGAUSS / STOCHVOL / GORDON / THETALOGISTIC / DISCRETECOX: M trajectories by
  * backward sampling over the t steps executed so far (smoothing.py:278-350): SMC_BACKWARD_ON2 is the exact O(N) draw per
  * trajectory and step (backward_sampling_ON2), SMC_BACKWARD_MCMC `nsteps` independent Metropolis steps with proposals
@@ -505,6 +506,24 @@ int smc_filter_backward_sample(smc_filter* f, int island, int method, int64_t M,
                                const int64_t* idx_last_host, const double* u_last_host,
                                const double* u_host, const double* u_acc_host,
                                int64_t* idx_out_host, double* paths_out_host);
+/* The same filters: M trajectories by the hybrid of rejection and exact backward sampling (backward_sampling_reject,
+ * smoothing.py:352-423; Dau & Chopin 2022).  Per step s = t-2 .. 0 and trajectory m, trial i = 0 .. max_trials-1 proposes
+ * prop_i from W_s and accepts iff log(u_acc[i]) < log p_{s+1}(x_{s+1} | X_s[prop_i]) - log_bound_host[s]; idx[s, m] is the
+ * proposal of the smallest accepted i, else the exact draw SMC_BACKWARD_ON2 makes from the same row s+1 with the same
+ * uniform (u_host / Philox stream 3): the law is the FFBS law for any bound that holds.  log_bound_host (t-1): entry s-1
+ * = log C_s with p_s(x | x') <= C_s, s = 1 .. t-1, the caller's (a NaN or +inf entry accepts nothing).
+ * max_trials is held to 2^24 - 1.  u_prop_host / u_acc_host (t-1, max_trials, M): replay tapes or NULL (Philox stream 4,
+ * key `seed`, counter (m, s, island, 4 | i << 8): word x01 -> [0, 1) proposal, word x23 -> (0, 1) acceptance);
+ * idx_last_host / u_last_host / u_host (t-1, M) as for smc_filter_backward_sample.  nprops_out_host / nexact_out_host (t-1)
+ * or NULL: trials made and trajectories drawn exactly per step (acc_rate[s] = (M - nexact[s]) / nprops[s]).
+ * SMC_ERR_INVALID: as smc_filter_backward_sample, max_trials < 1, log_bound_host NULL with t >= 2. */
+int smc_filter_backward_reject(smc_filter* f, int island, int64_t M, int64_t max_trials, uint64_t seed,
+                               const double* log_bound_host,
+                               const int64_t* idx_last_host, const double* u_last_host,
+                               const double* u_prop_host, const double* u_acc_host,
+                               const double* u_host,
+                               int64_t* idx_out_host, double* paths_out_host,
+                               int64_t* nprops_out_host, int64_t* nexact_out_host);
 int smc_filter_info(smc_filter* f, double* bytes_per_particle_step,
                     int* kernels_per_step);
 /* Average duration (ms) of the step's two parts -- the propagate kernel ("move") and the

@@ -25,7 +25,8 @@ MODEL_SVLEVERAGE = 6
 MODEL_DISCRETECOX = 7
 FK_BOOTSTRAP, FK_GUIDED, FK_APF, FK_APF_BOOT = 0, 1, 2, 3
 FIELD_X, FIELD_XP, FIELD_A, FIELD_LW, FIELD_W = range(5)
-BACKWARD_ON2, BACKWARD_MCMC = 0, 1
+BACKWARD_ON2, BACKWARD_MCMC, BACKWARD_REJECT = 0, 1, 2
+REJECT_MAX_TRIALS = 2 ** 24 - 1
 SUMMARY_COLS = 5
 PARAM_STRIDE = 16
 
@@ -163,6 +164,8 @@ SIGNATURES = {
     "smc_filter_trajectories": (c_int, [c_vp, c_int, P(c_i64)]),
     "smc_filter_backward_sample": (c_int, [c_vp, c_int, c_int, c_i64, c_int, c_u64, P(c_i64), P(c_dbl), P(c_dbl),
                                            P(c_dbl), P(c_i64), P(c_dbl)]),
+    "smc_filter_backward_reject": (c_int, [c_vp, c_int, c_i64, c_i64, c_u64, P(c_dbl), P(c_i64), P(c_dbl), P(c_dbl),
+                                           P(c_dbl), P(c_dbl), P(c_i64), P(c_dbl), P(c_i64), P(c_i64)]),
     "smc_filter_spacings": (c_int, [c_vp, c_i64, c_int, P(c_dbl)]),
     "smc_filter_info": (c_int, [c_vp, P(c_dbl), P(c_int)]),
     "smc_filter_profile": (c_int, [c_vp, c_int]),

@@ -168,6 +168,9 @@ class ParticleHistory(RollingParticleHistory):
     def backward_sampling_mcmc(self, M, nsteps=1, **kw):
         return self.backward_sampling_ON2(M, **kw)
 
+    def backward_sampling_reject(self, M, max_trials=None, **kw):
+        return self.backward_sampling_ON2(M, **kw)
+
 
 class _LazySteps:
     """Sequence over the steps run so far whose items are fetched from the device
@@ -282,18 +285,47 @@ class DeviceParticleHistory:
         """
         return self._backward(_lib.BACKWARD_MCMC, M, nsteps, seed, island, replay, return_idx)
 
+    def backward_sampling_reject(self, M, max_trials=None, seed=None, island=0, replay=None, return_idx=False):
+        """Hybrid rejection backward sampling (smoothing.py:352-423; Dau & Chopin 2022), on the device: per
+        trajectory and step at most ``max_trials`` rejection trials -- a proposal drawn from W_t is accepted with
+        probability p_{t+1}(x_{t+1} | proposal) / C_{t+1} -- then the exact draw of ``backward_sampling_ON2`` for
+        whatever is left.  The law is exactly the FFBS law; the expected cost per trajectory and step is O(1)
+        where the bound is not loose.  ``log C_t`` is ``fk.upper_bound_trans(t)``, evaluated on the host: the
+        stock univariate Gaussian models define it, a subclass may override ``upper_bound_log_pt``.
+
+        max_trials : None: M (the reference's default).  Held to 2**24 - 1: "pure rejection" (``inf``) is served
+            as that many trials followed by the exact draw, which is still the exact law.
+        seed : Philox key: trial i of trajectory m at step t draws from counter (m, t, island, 4 | i << 8), the
+            last row and the exact draws from stream 3 as ``backward_sampling_ON2``.
+        replay : ``idx_last`` / ``u_last`` as for ON2, ``u_prop`` and ``u_acc`` (T-1, max_trials, M) for the trials,
+            ``u`` (T-1, M) for the exact draws.
+
+        Returns what ``backward_sampling_ON2`` returns and sets ``acc_rate`` (T-1,) = (M - nexact) / nprops
+        (smoothing.py:422), ``nprops`` (trials made) and ``nexact`` (trajectories drawn exactly) per step.
+        The proposals have the law of the reference's ``MultinomialQueue`` draws; its NumPy permutation stream
+        is not reproduced.
+        """
+        if max_trials is None:
+            max_trials = M
+        max_trials = int(min(max_trials, _lib.REJECT_MAX_TRIALS))
+        return self._backward(_lib.BACKWARD_REJECT, M, max_trials, seed, island, replay, return_idx)
+
     def _backward(self, method, M, nsteps, seed, island, replay, return_idx):
+        """``nsteps``: Metropolis steps (MCMC) or max_trials (rejection)."""
         smc = self._smc
         M, nsteps, T = int(M), int(nsteps), smc._n
         if seed is None:
             from .core import _default_seed
             seed = _default_seed()
         replay = dict(replay or {})
-        shape = (max(T - 1, 0), M) if method == _lib.BACKWARD_ON2 else (max(T - 1, 0), nsteps, M)
+        on2, reject = method == _lib.BACKWARD_ON2, method == _lib.BACKWARD_REJECT
+        shape = (max(T - 1, 0), M) if on2 else (max(T - 1, 0), nsteps, M)
         names = {"idx_last": ((M,), np.int64), "u_last": ((M,), np.float64),
-                 ("u" if method == _lib.BACKWARD_ON2 else "u_prop"): (shape, np.float64)}
-        if method == _lib.BACKWARD_MCMC:
+                 ("u" if on2 else "u_prop"): (shape, np.float64)}
+        if not on2:
             names["u_acc"] = (shape, np.float64)
+        if reject:
+            names["u"] = ((max(T - 1, 0), M), np.float64)
         unknown = set(replay) - set(names)
         if unknown:
             raise ValueError("backward sampling: unknown replay tape(s) %s" % sorted(unknown))
@@ -309,12 +341,23 @@ class DeviceParticleHistory:
         ptr = lambda a, ct: a.ctypes.data_as(_lib.P(ct)) if a is not None else None
         idx = np.empty((T, max(M, 0)), dtype=np.int64)
         paths = np.empty((T, max(M, 0)))
+        seed = int(seed) & (2 ** 64 - 1)
+        last = (ptr(tapes["idx_last"], _lib.c_i64), ptr(tapes["u_last"], _lib.c_dbl))
+        out = (ptr(idx, _lib.c_i64), ptr(paths, _lib.c_dbl))
         try:
-            _lib.check(_lib.lib().smc_filter_backward_sample(
-                smc._f, int(island), method, M, nsteps, int(seed) & (2 ** 64 - 1),
-                ptr(tapes["idx_last"], _lib.c_i64), ptr(tapes["u_last"], _lib.c_dbl),
-                ptr(tapes.get("u", tapes.get("u_prop")), _lib.c_dbl), ptr(tapes.get("u_acc"), _lib.c_dbl),
-                ptr(idx, _lib.c_i64), ptr(paths, _lib.c_dbl)))
+            if reject:
+                log_bound = np.array([self.fk.upper_bound_trans(s) for s in range(1, T)], dtype=np.float64).reshape(-1)
+                nprops, nexact = np.zeros(max(T - 1, 0), dtype=np.int64), np.zeros(max(T - 1, 0), dtype=np.int64)
+                _lib.check(_lib.lib().smc_filter_backward_reject(
+                    smc._f, int(island), M, nsteps, seed, ptr(log_bound, _lib.c_dbl), *last,
+                    ptr(tapes["u_prop"], _lib.c_dbl), ptr(tapes["u_acc"], _lib.c_dbl), ptr(tapes["u"], _lib.c_dbl),
+                    *out, ptr(nprops, _lib.c_i64), ptr(nexact, _lib.c_i64)))
+                self.nprops, self.nexact = nprops, nexact
+                self.acc_rate = (M - nexact) / nprops
+            else:
+                _lib.check(_lib.lib().smc_filter_backward_sample(
+                    smc._f, int(island), method, M, nsteps, seed, *last,
+                    ptr(tapes.get("u", tapes.get("u_prop")), _lib.c_dbl), ptr(tapes.get("u_acc"), _lib.c_dbl), *out))
         except ValueError as e:
             if "model kind" in str(e):
                 raise NotImplementedError(str(e)) from None

@@ -1965,30 +1965,137 @@ int smc_filter_one_trajectory(smc_filter* f, int island, int64_t n_last, double*
 }
 
 // Backward sampling over the resident history (smc_smooth.h).  Workspaces come from the context's pool and are used
-// on its stream only; the one synchronisation is the download at the end.
+// on its stream only; the one synchronisation is the download at the end.  The sm_* helpers serve both entries
+// (`who` names the entry in the message, as SMC_REQUIRE does).
+#define SM_REQUIRE(who, cond, msg)                             \
+    do {                                                       \
+        if (!(cond)) {                                         \
+            smc_set_error("%s: %s", who, msg);                 \
+            return SMC_ERR_INVALID;                            \
+        }                                                      \
+    } while (0)
+static int sm_check_filter(const char* who, smc_filter* f, int island, const void* idx_out_host)
+{
+    SM_REQUIRE(who, f && idx_out_host, "null argument");
+    SM_REQUIRE(who, !f->plan.sqmc(), "SQMC filters are not supported (backward_sampling_qmc is a different algorithm)");
+    SM_REQUIRE(who, f->kind != SMC_MODEL_SVLEVERAGE, "model kind SVLEVERAGE is not supported: its transition reads y_{t-1}");
+    SM_REQUIRE(who, f->kind != SMC_MODEL_MVLINGAUSS, "model kind MVLINGAUSS is not supported: univariate models only");
+    SM_REQUIRE(who, f->kind == SMC_MODEL_LINGAUSS || f->kind == SMC_MODEL_STOCHVOL || f->kind == SMC_MODEL_GORDON ||
+               f->kind == SMC_MODEL_THETALOGISTIC || f->kind == SMC_MODEL_DISCRETECOX, "model kind is not supported");
+    SM_REQUIRE(who, f->a.hist == 1, "the filter was created without a whole history (keep_history = 1)");
+    SM_REQUIRE(who, island >= 0 && island < f->a.n_islands, "island out of range");
+    return SMC_OK;
+}
+static int sm_check_trajectories(const char* who, smc_filter* f, int64_t M)
+{
+    SM_REQUIRE(who, M >= 1 && M < ((int64_t)1 << 31), "M must be at least 1 (and below 2^31)");
+    return SMC_OK;
+}
+static int sm_check_steps(const char* who, smc_filter* f)
+{
+    SM_REQUIRE(who, f->t_host >= 1, "no step has run yet");
+    return SMC_OK;
+}
+static int sm_check_idx_last(const char* who, smc_filter* f, int64_t M, const int64_t* idx_last_host)
+{
+    if (idx_last_host)
+        for (i64 m = 0; m < M; ++m) SM_REQUIRE(who, idx_last_host[m] >= 0 && idx_last_host[m] < f->a.N, "idx_last out of range");
+    return SMC_OK;
+}
+// what every launch of one call shares
+static SmArgs sm_args(smc_filter* f, int island, int64_t M, uint64_t seed, const u64* cdf)
+{
+    SmArgs s{};
+    s.p = f->a.params + (size_t)island * PARAM_STRIDE;
+    s.N = f->a.N; s.M = M;
+    s.seed = seed;
+    s.island = (u32)(f->a.island_offset + island);
+    s.kform = f->plan.two_level ? 1 : 0;
+    s.shift = sm_shift(f->a.N);
+    s.nsteps = 1;
+    s.cdf = cdf;
+    return s;
+}
+static const double* sm_rows(smc_filter* f, int island)
+{
+    return f->a.summ + (size_t)island * (f->a.T + 1) * SUMM_STRIDE;
+}
+// cdf = the integer CDF of W_step
+static void sm_weights_cdf(smc_filter* f, int island, i64 step, const SmArgs& s, u64* tot, u64* cdf)
+{
+    const i64 N = f->a.N;
+    const unsigned nch = (unsigned)((N + SM_CHUNK - 1) / SM_CHUNK);
+    const double* lw = f_lw(f->a, step) + (size_t)island * N;
+    const double* row = sm_rows(f, island) + (size_t)step * SUMM_STRIDE;
+    hipStream_t st = f->ctx->stream;
+    SMC_LAUNCH(k_sm_cdf_totals, dim3(nch), dim3(SMC_BLOCK), st, lw, row, N, s.kform, s.shift, tot);
+    SMC_LAUNCH(k_sm_cdf_scan, dim3(nch), dim3(SMC_BLOCK), st, lw, row, N, s.kform, s.shift, (const u64*)tot, cdf);
+}
+// last row: M iid draws from W_{t-1} (smoothing.py:278-281), or the caller's indices
+static int sm_last_row(smc_filter* f, int island, SmArgs& s, i64* idx, const int64_t* idx_last_host, const double* d_ulast,
+                       u64* tot, u64* cdf)
+{
+    const i64 t = f->t_host, M = s.M;
+    hipStream_t st = f->ctx->stream;
+    if (idx_last_host) {
+        SMC_HIP_CHECK(hipMemcpyAsync(idx + (size_t)(t - 1) * M, idx_last_host, (size_t)M * 8, hipMemcpyHostToDevice, st));
+    } else {
+        sm_weights_cdf(f, island, t - 1, s, tot, cdf);
+        s.t = (u32)(t - 1);
+        s.u = d_ulast;
+        s.idx_out = idx + (size_t)(t - 1) * M;
+        SMC_LAUNCH(k_sm_draw_last, dim3((unsigned)((M + SMC_BLOCK - 1) / SMC_BLOCK)), dim3(SMC_BLOCK), st, s);
+    }
+    return SMC_OK;
+}
+// the history pointers of backward step b: X_b, lw_b against the row drawn for step b + 1
+static void sm_step_args(smc_filter* f, int island, i64 b, i64* idx, SmArgs& s)
+{
+    const i64 N = f->a.N;
+    const double* rows = sm_rows(f, island);
+    s.t = (u32)b;
+    s.Xt = f_X(f->a, b) + (size_t)island * N;
+    s.lwt = f_lw(f->a, b) + (size_t)island * N;
+    s.Xn = f_X(f->a, b + 1) + (size_t)island * N;
+    s.An = f_A(f->a, b + 1) + (size_t)island * N;
+    s.rowt = rows + (size_t)b * SUMM_STRIDE;
+    s.rown = rows + (size_t)(b + 1) * SUMM_STRIDE;
+    s.aux = f->a.aux ? f->a.aux + (b + 1) : nullptr;
+    s.idx_next = idx + (size_t)(b + 1) * s.M;
+    s.idx_out = idx + (size_t)b * s.M;
+}
+// paths = X_s[idx[s]] if asked for, then the one download and synchronisation of a call
+static int sm_download(smc_filter* f, int island, i64 M, const i64* idx, double* paths, int64_t* idx_out_host,
+                       double* paths_out_host)
+{
+    const i64 t = f->t_host;
+    hipStream_t st = f->ctx->stream;
+    if (paths)
+        SMC_LAUNCH(k_sm_paths, dim3((unsigned)(((size_t)t * M + SMC_BLOCK - 1) / SMC_BLOCK)), dim3(SMC_BLOCK), st, f->a, island,
+                   t, (i64)M, idx, paths);
+    SMC_LAUNCH_CHECK();
+    SMC_HIP_CHECK(hipMemcpyAsync(idx_out_host, idx, (size_t)t * M * 8, hipMemcpyDeviceToHost, st));
+    if (paths) SMC_HIP_CHECK(hipMemcpyAsync(paths_out_host, paths, (size_t)t * M * 8, hipMemcpyDeviceToHost, st));
+    SMC_HIP_CHECK(hipStreamSynchronize(st));
+    return SMC_OK;
+}
+
 int smc_filter_backward_sample(smc_filter* f, int island, int method, int64_t M, int nsteps, uint64_t seed,
                                const int64_t* idx_last_host, const double* u_last_host,
                                const double* u_host, const double* u_acc_host,
                                int64_t* idx_out_host, double* paths_out_host)
 {
     if (f) { (void)hipSetDevice(f->ctx->device); flush_rows(f); }
-    SMC_REQUIRE(f && idx_out_host, "null argument");
-    SMC_REQUIRE(!f->plan.sqmc(), "SQMC filters are not supported (backward_sampling_qmc is a different algorithm)");
-    SMC_REQUIRE(f->kind != SMC_MODEL_SVLEVERAGE, "model kind SVLEVERAGE is not supported: its transition reads y_{t-1}");
-    SMC_REQUIRE(f->kind != SMC_MODEL_MVLINGAUSS, "model kind MVLINGAUSS is not supported: univariate models only");
-    SMC_REQUIRE(f->kind == SMC_MODEL_LINGAUSS || f->kind == SMC_MODEL_STOCHVOL || f->kind == SMC_MODEL_GORDON ||
-                f->kind == SMC_MODEL_THETALOGISTIC || f->kind == SMC_MODEL_DISCRETECOX, "model kind is not supported");
-    SMC_REQUIRE(f->a.hist == 1, "the filter was created without a whole history (keep_history = 1)");
-    SMC_REQUIRE(island >= 0 && island < f->a.n_islands, "island out of range");
+    int rc = sm_check_filter(__func__, f, island, idx_out_host);
+    if (rc != SMC_OK) return rc;
     SMC_REQUIRE(method == SMC_BACKWARD_ON2 || method == SMC_BACKWARD_MCMC, "unknown method");
-    SMC_REQUIRE(M >= 1 && M < ((int64_t)1 << 31), "M must be at least 1 (and below 2^31)");
+    if ((rc = sm_check_trajectories(__func__, f, M)) != SMC_OK) return rc;
     SMC_REQUIRE(nsteps >= 1, "nsteps must be at least 1");
-    const i64 t = f->t_host, N = f->a.N, T = f->a.T;
-    SMC_REQUIRE(t >= 1, "no step has run yet");
+    const i64 t = f->t_host, N = f->a.N;
+    if ((rc = sm_check_steps(__func__, f)) != SMC_OK) return rc;
     if (method == SMC_BACKWARD_ON2) nsteps = 1;
     SMC_REQUIRE((i64)nsteps * M < ((i64)1 << 32), "nsteps * M must stay below 2^32 (Philox counter)");
-    if (idx_last_host)
-        for (i64 m = 0; m < M; ++m) SMC_REQUIRE(idx_last_host[m] >= 0 && idx_last_host[m] < N, "idx_last out of range");
+    if ((rc = sm_check_idx_last(__func__, f, M, idx_last_host)) != SMC_OK) return rc;
     hipStream_t st = f->ctx->stream;
     SmPool pool(f->ctx);
     const bool mcmc = method == SMC_BACKWARD_MCMC;
@@ -1997,7 +2104,7 @@ int smc_filter_backward_sample(smc_filter* f, int island, int method, int64_t M,
     i64* idx = nullptr;
     u64 *cdf = nullptr, *tot = nullptr;
     double *paths = nullptr, *d_ulast = nullptr, *d_u = nullptr, *d_uacc = nullptr;
-    int rc = pool.get((size_t)t * M, &idx);
+    rc = pool.get((size_t)t * M, &idx);
     if (rc == SMC_OK && need_cdf) rc = pool.get((size_t)N, &cdf);
     if (rc == SMC_OK && need_cdf) rc = pool.get((size_t)nch, &tot);
     if (rc == SMC_OK && paths_out_host) rc = pool.get((size_t)t * M, &paths);
@@ -2008,46 +2115,14 @@ int smc_filter_backward_sample(smc_filter* f, int island, int method, int64_t M,
     if (rc != SMC_OK) return rc;
     SMC_HIP_CHECK(hipMemsetAsync(idx, 0, (size_t)t * M * 8, st));          // (every index a kernel reads is in range)
 
-    const double* rows = f->a.summ + (size_t)island * (T + 1) * SUMM_STRIDE;
-    SmArgs s{};
-    s.p = f->a.params + (size_t)island * PARAM_STRIDE;
-    s.N = N; s.M = M;
-    s.seed = seed;
-    s.island = (u32)(f->a.island_offset + island);
-    s.kform = f->plan.two_level ? 1 : 0;
-    s.shift = sm_shift(N);
+    SmArgs s = sm_args(f, island, M, seed, cdf);
     s.nsteps = nsteps;
-    s.cdf = cdf;
-    auto weights_cdf = [&](i64 step) {
-        const double* lw = f_lw(f->a, step) + (size_t)island * N;
-        const double* row = rows + (size_t)step * SUMM_STRIDE;
-        SMC_LAUNCH(k_sm_cdf_totals, dim3(nch), dim3(SMC_BLOCK), st, lw, row, N, s.kform, s.shift, tot);
-        SMC_LAUNCH(k_sm_cdf_scan, dim3(nch), dim3(SMC_BLOCK), st, lw, row, N, s.kform, s.shift, (const u64*)tot, cdf);
-    };
-    // last row: M iid draws from W_{t-1} (smoothing.py:278-281)
-    if (idx_last_host) {
-        SMC_HIP_CHECK(hipMemcpyAsync(idx + (size_t)(t - 1) * M, idx_last_host, (size_t)M * 8, hipMemcpyHostToDevice, st));
-    } else {
-        weights_cdf(t - 1);
-        s.t = (u32)(t - 1);
-        s.u = d_ulast;
-        s.idx_out = idx + (size_t)(t - 1) * M;
-        SMC_LAUNCH(k_sm_draw_last, dim3((unsigned)((M + SMC_BLOCK - 1) / SMC_BLOCK)), dim3(SMC_BLOCK), st, s);
-    }
+    if ((rc = sm_last_row(f, island, s, idx, idx_last_host, d_ulast, tot, cdf)) != SMC_OK) return rc;
     for (i64 b = t - 2; b >= 0; --b) {
-        if (mcmc) weights_cdf(b);
-        s.t = (u32)b;
-        s.Xt = f_X(f->a, b) + (size_t)island * N;
-        s.lwt = f_lw(f->a, b) + (size_t)island * N;
-        s.Xn = f_X(f->a, b + 1) + (size_t)island * N;
-        s.An = f_A(f->a, b + 1) + (size_t)island * N;
-        s.rowt = rows + (size_t)b * SUMM_STRIDE;
-        s.rown = rows + (size_t)(b + 1) * SUMM_STRIDE;
-        s.aux = f->a.aux ? f->a.aux + (b + 1) : nullptr;
+        if (mcmc) sm_weights_cdf(f, island, b, s, tot, cdf);
+        sm_step_args(f, island, b, idx, s);
         s.u = d_u ? d_u + (size_t)b * per_step : nullptr;
         s.u_acc = d_uacc ? d_uacc + (size_t)b * per_step : nullptr;
-        s.idx_next = idx + (size_t)(b + 1) * M;
-        s.idx_out = idx + (size_t)b * M;
         switch (f->kind) {
         case SMC_MODEL_LINGAUSS: sm_launch_step<SMC_MODEL_LINGAUSS>(method, st, s); break;
         case SMC_MODEL_STOCHVOL: sm_launch_step<SMC_MODEL_STOCHVOL>(method, st, s); break;
@@ -2056,13 +2131,85 @@ int smc_filter_backward_sample(smc_filter* f, int island, int method, int64_t M,
         default: sm_launch_step<SMC_MODEL_DISCRETECOX>(method, st, s); break;
         }
     }
-    if (paths)
-        SMC_LAUNCH(k_sm_paths, dim3((unsigned)(((size_t)t * M + SMC_BLOCK - 1) / SMC_BLOCK)), dim3(SMC_BLOCK), st, f->a, island,
-                   t, (i64)M, (const i64*)idx, paths);
-    SMC_LAUNCH_CHECK();
-    SMC_HIP_CHECK(hipMemcpyAsync(idx_out_host, idx, (size_t)t * M * 8, hipMemcpyDeviceToHost, st));
-    if (paths) SMC_HIP_CHECK(hipMemcpyAsync(paths_out_host, paths, (size_t)t * M * 8, hipMemcpyDeviceToHost, st));
-    SMC_HIP_CHECK(hipStreamSynchronize(st));
+    return sm_download(f, island, M, idx, paths, idx_out_host, paths_out_host);
+}
+
+// The hybrid of rejection trials and the exact draw (smc_smooth.h, k_sm_reject_*).  Per backward step: the CDF of W_b,
+// then three launches whose grids the host sizes by M -- the lists' counts are read on the device, so the loop has no
+// synchronisation.  The counters of all steps are zeroed once, in front of the loop.
+int smc_filter_backward_reject(smc_filter* f, int island, int64_t M, int64_t max_trials, uint64_t seed,
+                               const double* log_bound_host,
+                               const int64_t* idx_last_host, const double* u_last_host,
+                               const double* u_prop_host, const double* u_acc_host,
+                               const double* u_host,
+                               int64_t* idx_out_host, double* paths_out_host,
+                               int64_t* nprops_out_host, int64_t* nexact_out_host)
+{
+    if (f) { (void)hipSetDevice(f->ctx->device); flush_rows(f); }
+    int rc = sm_check_filter(__func__, f, island, idx_out_host);
+    if (rc != SMC_OK) return rc;
+    if ((rc = sm_check_trajectories(__func__, f, M)) != SMC_OK) return rc;
+    SMC_REQUIRE(max_trials >= 1, "max_trials must be at least 1");
+    if ((rc = sm_check_steps(__func__, f)) != SMC_OK) return rc;
+    const i64 t = f->t_host, N = f->a.N;
+    SMC_REQUIRE(t < 2 || log_bound_host, "null log_bound: the bounds log C_s, s = 1 .. t - 1, are the caller's");
+    if ((rc = sm_check_idx_last(__func__, f, M, idx_last_host)) != SMC_OK) return rc;
+    if (max_trials > SM_REJ_MAX_TRIALS) max_trials = SM_REJ_MAX_TRIALS;    // then the exact draw: still the exact law
+    hipStream_t st = f->ctx->stream;
+    SmPool pool(f->ctx);
+    const unsigned nch = (unsigned)((N + SM_CHUNK - 1) / SM_CHUNK);
+    const size_t nb = (size_t)(t - 1);                                       // backward steps
+    i64* idx = nullptr;
+    u64 *cdf = nullptr, *tot = nullptr, *ctr = nullptr;
+    u32 *listA = nullptr, *listB = nullptr;
+    double *paths = nullptr, *d_ulast = nullptr, *d_u = nullptr, *d_uprop = nullptr, *d_uacc = nullptr, *d_logC = nullptr;
+    rc = pool.get((size_t)t * M, &idx);
+    if (rc == SMC_OK) rc = pool.get((size_t)N, &cdf);
+    if (rc == SMC_OK) rc = pool.get((size_t)nch, &tot);
+    if (rc == SMC_OK) rc = pool.get(nb * SM_CTR_STRIDE, &ctr);
+    if (rc == SMC_OK) rc = pool.get((size_t)M, &listA);
+    if (rc == SMC_OK) rc = pool.get((size_t)M, &listB);
+    if (rc == SMC_OK && paths_out_host) rc = pool.get((size_t)t * M, &paths);
+    if (rc == SMC_OK && !idx_last_host) rc = pool.upload(u_last_host, (size_t)M, &d_ulast);
+    const size_t per_step = (size_t)max_trials * M;
+    if (rc == SMC_OK && nb) rc = pool.upload(log_bound_host, nb, &d_logC);
+    if (rc == SMC_OK) rc = pool.upload(u_host, nb * M, &d_u);
+    if (rc == SMC_OK) rc = pool.upload(u_prop_host, nb * per_step, &d_uprop);
+    if (rc == SMC_OK) rc = pool.upload(u_acc_host, nb * per_step, &d_uacc);
+    if (rc != SMC_OK) return rc;
+    SMC_HIP_CHECK(hipMemsetAsync(idx, 0, (size_t)t * M * 8, st));          // (every index a kernel reads is in range)
+    SMC_HIP_CHECK(hipMemsetAsync(ctr, 0, (nb ? nb : 1) * SM_CTR_STRIDE * 8, st));
+
+    SmArgs s = sm_args(f, island, M, seed, cdf);
+    if ((rc = sm_last_row(f, island, s, idx, idx_last_host, d_ulast, tot, cdf)) != SMC_OK) return rc;
+    SmRej r{};
+    r.listA = listA; r.listB = listB;
+    r.max_trials = max_trials;
+    r.solo = max_trials < sm_reject_solo_trials() ? max_trials : sm_reject_solo_trials();
+    for (i64 b = t - 2; b >= 0; --b) {
+        sm_weights_cdf(f, island, b, s, tot, cdf);
+        sm_step_args(f, island, b, idx, s);
+        s.u = d_u ? d_u + (size_t)b * M : nullptr;
+        r.u_prop = d_uprop ? d_uprop + (size_t)b * per_step : nullptr;
+        r.u_acc = d_uacc ? d_uacc + (size_t)b * per_step : nullptr;
+        r.logC = d_logC + b;
+        r.ctr = ctr + (size_t)b * SM_CTR_STRIDE;
+        switch (f->kind) {
+        case SMC_MODEL_LINGAUSS: sm_launch_reject<SMC_MODEL_LINGAUSS>(st, s, r); break;
+        case SMC_MODEL_STOCHVOL: sm_launch_reject<SMC_MODEL_STOCHVOL>(st, s, r); break;
+        case SMC_MODEL_GORDON: sm_launch_reject<SMC_MODEL_GORDON>(st, s, r); break;
+        case SMC_MODEL_THETALOGISTIC: sm_launch_reject<SMC_MODEL_THETALOGISTIC>(st, s, r); break;
+        default: sm_launch_reject<SMC_MODEL_DISCRETECOX>(st, s, r); break;
+        }
+    }
+    std::vector<u64> counts(nb * SM_CTR_STRIDE);
+    if (nb && (nprops_out_host || nexact_out_host))
+        SMC_HIP_CHECK(hipMemcpyAsync(counts.data(), ctr, nb * SM_CTR_STRIDE * 8, hipMemcpyDeviceToHost, st));
+    if ((rc = sm_download(f, island, M, idx, paths, idx_out_host, paths_out_host)) != SMC_OK) return rc;
+    for (size_t b = 0; b < nb; ++b) {
+        if (nprops_out_host) nprops_out_host[b] = (int64_t)counts[b * SM_CTR_STRIDE + SM_CTR_NPROPS];
+        if (nexact_out_host) nexact_out_host[b] = (int64_t)counts[b * SM_CTR_STRIDE + SM_CTR_NEXACT];
+    }
     return SMC_OK;
 }
 

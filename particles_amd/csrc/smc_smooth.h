@@ -1,7 +1,8 @@
 // smc_smooth.h -- backward sampling over the resident particle history (keep_history = 1):
-// particles/smoothing.py:278-350, ParticleHistory.backward_sampling_ON2 (exact FFBS) and
-// backward_sampling_mcmc (independent Metropolis steps, Dau & Chopin 2022).  Host side:
-// smc_filter_backward_sample in smc_filter.hip.  The kernels read the history and write their
+// particles/smoothing.py:278-423, ParticleHistory.backward_sampling_ON2 (exact FFBS),
+// backward_sampling_mcmc (independent Metropolis steps, Dau & Chopin 2022) and backward_sampling_reject
+// (their hybrid: rejection trials, then the exact draw).  Host side: smc_filter_backward_sample and
+// smc_filter_backward_reject in smc_filter.hip.  The kernels read the history and write their
 // own workspaces only.
 //
 // Every draw is an inverse-CDF lookup of ONE uniform in an INTEGER CDF, so the drawn index is a
@@ -17,7 +18,8 @@
 //
 // Uniforms: a replay tape, or Philox stream SMC_STREAM_BACKWARD with counter
 // (i M + m, t, island, 3): word x01 -> [0, 1) (index / proposal), word x23 -> (0, 1) (acceptance);
-// i = Metropolis step, 0 for ON2 and for the last row.
+// i = Metropolis step, 0 for ON2 and for the last row.  Rejection trials have a stream of their own
+// (SMC_STREAM_REJECT, see k_sm_reject_solo).
 #pragma once
 #include "smc_filter_kernels.h"
 
@@ -184,13 +186,14 @@ __global__ void __launch_bounds__(SMC_BLOCK) k_sm_draw_last(const SmArgs s)
 // each (cheaper than N words per trajectory through memory).  Wave w owns the contiguous quarter
 // [w R, (w + 1) R) of the particles, R a multiple of 64: its lanes read consecutive particles, and the
 // third sweep is walked by the one wave whose quarter holds the threshold, until it is found.
+// sm_on2_draw is the body of both k_sm_on2 (m = blockIdx.x) and k_sm_reject_exact (m from list B).  A wave
+// returns from it after the last barrier, which is safe only because a workgroup draws for ONE trajectory:
+// do not call it in a loop.
 // ---------------------------------------------------------------------------
 template <int KIND>
-__global__ void __launch_bounds__(SMC_BLOCK) k_sm_on2(const SmArgs s)
+__device__ __forceinline__ void sm_on2_draw(const SmArgs& s, const i64 m, double* smd, u64* smu)
 {
-    __shared__ double smd[SMC_SM];
-    __shared__ u64 smu[SMC_SM];
-    const i64 m = (i64)blockIdx.x, N = s.N;
+    const i64 N = s.N;
     const SmTrans<KIND> tr(s);
     const double xn = smc_ldg(s.Xn + smc_ldg(s.idx_next + m));
     double mx = -INFINITY;
@@ -246,6 +249,13 @@ __global__ void __launch_bounds__(SMC_BLOCK) k_sm_on2(const SmArgs s)
         if (run > thr) break;
     }
 }
+template <int KIND>
+__global__ void __launch_bounds__(SMC_BLOCK) k_sm_on2(const SmArgs s)
+{
+    __shared__ double smd[SMC_SM];
+    __shared__ u64 smu[SMC_SM];
+    sm_on2_draw<KIND>(s, (i64)blockIdx.x, smd, smu);
+}
 
 // ---------------------------------------------------------------------------
 // MCMC backward step (smoothing.py:340-349): one thread per trajectory; start from the ancestor of the
@@ -273,6 +283,126 @@ __global__ void __launch_bounds__(SMC_BLOCK) k_sm_mcmc(const SmArgs s)
         }
     }
     s.idx_out[m] = cur;
+}
+
+// ---------------------------------------------------------------------------
+// hybrid rejection step (smoothing.py:352-423, backward_sampling_reject; Dau & Chopin 2022).  Trial i of
+// trajectory m proposes prop_i = sm_search(cdf(W_t), u_prop[i]) and accepts iff
+//   log(u_acc[i]) < log p_{t+1}(xn | X_t[prop_i]) - log C_{t+1};
+// idx[t, m] = prop_i of the smallest accepted i < max_trials, else the exact draw of sm_on2_draw with ITS uniform.
+// Three launches, ordered by the stream alone (no kernel waits for another workgroup):
+//   k_sm_reject_solo   one thread per trajectory runs trials 0 .. solo - 1; the unresolved go to list A
+//   k_sm_reject_wave   one wave per entry of A: 64 trials a round, the lowest accepted lane wins -- the index a
+//                      sequential loop finds; a trajectory out of trials goes to list B
+//   k_sm_reject_exact  one workgroup per entry of B
+// The order of a list is arbitrary; nothing reads it but the next launch.  ctr: the step's four u64 slots.
+// Uniforms of trial i: tapes (max_trials, M), or Philox counter (m, t, island, SMC_STREAM_REJECT | i << 8):
+// word x01 -> [0, 1) proposal, word x23 -> (0, 1) acceptance.
+// ---------------------------------------------------------------------------
+#define SM_REJ_SOLO 4                    /* trials of the one-thread-per-trajectory launch */
+#define SM_REJ_MAX_TRIALS 0xffffff       /* the trial index shares the stream word with SMC_STREAM_REJECT */
+enum { SM_CTR_A = 0, SM_CTR_B = 1, SM_CTR_NPROPS = 2, SM_CTR_NEXACT = 3, SM_CTR_STRIDE = 4 };
+
+struct SmRej {
+    const double *u_prop, *u_acc;   // replay tapes of this step (max_trials, M) or null: Philox
+    const double* logC;             // log C_{t+1}, one word
+    u64* ctr;                       // SM_CTR_* of this step
+    u32 *listA, *listB;             // (M) each
+    i64 max_trials, solo;           // solo = min(max_trials, trials of the first launch)
+};
+
+template <int KIND>
+__device__ __forceinline__ bool sm_rej_trial(const SmArgs& s, const SmRej& r, const SmTrans<KIND>& tr, i64 m, i64 i,
+                                             double xn, double logC, i64& prop)
+{
+    double u, ua;
+    if (r.u_prop && r.u_acc) {
+        u = smc_ldg(r.u_prop + i * s.M + m);
+        ua = smc_ldg(r.u_acc + i * s.M + m);
+    } else {
+        u64 a, b;
+        smc_philox((u32)m, s.t, s.island, SMC_STREAM_REJECT | ((u32)i << 8), s.seed, a, b);
+        u = r.u_prop ? smc_ldg(r.u_prop + i * s.M + m) : smc_u01_halfopen(a);
+        ua = r.u_acc ? smc_ldg(r.u_acc + i * s.M + m) : smc_u01_open(b);
+    }
+    prop = sm_search(s.cdf, s.N, u);
+    const double lp = tr.logpt(smc_ldg(s.Xt + prop), xn);
+    return log(ua) < lp - logC;                                  // (a NaN or +inf bound accepts nothing)
+}
+// lanes below `lane` of a ballot
+__device__ __forceinline__ int sm_rank(u64 mask, int lane) { return __popcll(mask & ((1ull << lane) - 1ull)); }
+
+template <int KIND>
+__global__ void __launch_bounds__(SMC_BLOCK) k_sm_reject_solo(const SmArgs s, const SmRej r)
+{
+    const i64 m = (i64)blockIdx.x * SMC_BLOCK + threadIdx.x;
+    const bool live = m < s.M;                                   // (every lane stays for the wave's ballot and sum)
+    const SmTrans<KIND> tr(s);
+    const double logC = smc_ldg(r.logC);
+    const double xn = live ? smc_ldg(s.Xn + smc_ldg(s.idx_next + m)) : 0.0;
+    bool open = live;
+    u64 ntrials = 0;
+    for (i64 i = 0; i < r.solo; ++i) {
+        if (open) {
+            i64 prop;
+            ++ntrials;
+            if (sm_rej_trial<KIND>(s, r, tr, m, i, xn, logC, prop)) {
+                s.idx_out[m] = prop;
+                open = false;
+            }
+        }
+    }
+    const u64 mask = __ballot(open ? 1 : 0);
+    const u64 sum = smc_wave_sum_u64(ntrials);
+    u64 at = 0;
+    if (smc_lane() == 0) {
+        if (sum) (void)atomicAdd(r.ctr + SM_CTR_NPROPS, sum);
+        if (mask) at = atomicAdd(r.ctr + SM_CTR_A, (u64)__popcll(mask));
+    }
+    at = smc_readlane64(at, 0);
+    if (open) r.listA[at + sm_rank(mask, smc_lane())] = (u32)m;  // (at + popcount <= M: one slot per trajectory)
+}
+
+template <int KIND>
+__global__ void __launch_bounds__(SMC_BLOCK) k_sm_reject_wave(const SmArgs s, const SmRej r)
+{
+    const u64 e = (u64)blockIdx.x * SMC_NWAVE + smc_wave();
+    if (e >= r.ctr[SM_CTR_A]) return;                            // wave-uniform; the kernel has no barrier
+    const i64 m = (i64)r.listA[e];
+    const SmTrans<KIND> tr(s);
+    const double logC = smc_ldg(r.logC);
+    const double xn = smc_ldg(s.Xn + smc_ldg(s.idx_next + m));
+    u64 ntrials = 0;
+    bool found = false;
+    for (i64 base = r.solo; base < r.max_trials; base += 64) {
+        const i64 i = base + smc_lane();
+        i64 prop = 0;
+        const bool acc = (i < r.max_trials) ? sm_rej_trial<KIND>(s, r, tr, m, i, xn, logC, prop) : false;
+        const u64 mask = __ballot(acc ? 1 : 0);
+        if (mask) {
+            const int win = __popcll(~mask & (mask - 1ull));     // the lowest accepted lane
+            if (smc_lane() == win) s.idx_out[m] = prop;
+            ntrials += (u64)win + 1;                             // (the speculative lanes behind it do not count)
+            found = true;
+            break;
+        }
+        ntrials += (u64)((r.max_trials - base < 64) ? r.max_trials - base : 64);
+    }
+    if (smc_lane() != 0) return;
+    if (ntrials) (void)atomicAdd(r.ctr + SM_CTR_NPROPS, ntrials);
+    if (!found) {
+        r.listB[atomicAdd(r.ctr + SM_CTR_B, 1ull)] = (u32)m;     // (at most one slot per entry of A)
+        (void)atomicAdd(r.ctr + SM_CTR_NEXACT, 1ull);
+    }
+}
+
+template <int KIND>
+__global__ void __launch_bounds__(SMC_BLOCK) k_sm_reject_exact(const SmArgs s, const SmRej r)
+{
+    __shared__ double smd[SMC_SM];
+    __shared__ u64 smu[SMC_SM];
+    if ((u64)blockIdx.x >= r.ctr[SM_CTR_B]) return;              // the whole workgroup, before its first barrier
+    sm_on2_draw<KIND>(s, (i64)r.listB[blockIdx.x], smd, smu);
 }
 
 // paths[t, m] = X_t[idx[t, m]]   (smoothing.py:288)
@@ -319,4 +449,20 @@ static void sm_launch_step(int method, hipStream_t st, const SmArgs& s)
         SMC_LAUNCH((k_sm_on2<KIND>), dim3((unsigned)s.M), dim3(SMC_BLOCK), st, s);
     else
         SMC_LAUNCH((k_sm_mcmc<KIND>), dim3((unsigned)((s.M + SMC_BLOCK - 1) / SMC_BLOCK)), dim3(SMC_BLOCK), st, s);
+}
+// Trials of the first launch.  SMC_REJECT_SOLO_TRIALS (measurements only, tools/ffbs_perf.py): a value >= max_trials
+// leaves the wave launch nothing but to pass the unresolved on.  The drawn indices do not depend on it.
+static i64 sm_reject_solo_trials()
+{
+    const char* e = getenv("SMC_REJECT_SOLO_TRIALS");
+    const long long v = e ? atoll(e) : 0;
+    return v >= 1 ? (i64)v : (i64)SM_REJ_SOLO;
+}
+template <int KIND>
+static void sm_launch_reject(hipStream_t st, const SmArgs& s, const SmRej& r)
+{
+    const unsigned M = (unsigned)s.M;                            // (the grids are sized by M: the lists' counts stay on the device)
+    SMC_LAUNCH((k_sm_reject_solo<KIND>), dim3((M + SMC_BLOCK - 1) / SMC_BLOCK), dim3(SMC_BLOCK), st, s, r);
+    SMC_LAUNCH((k_sm_reject_wave<KIND>), dim3((M + SMC_NWAVE - 1) / SMC_NWAVE), dim3(SMC_BLOCK), st, s, r);
+    SMC_LAUNCH((k_sm_reject_exact<KIND>), dim3(M), dim3(SMC_BLOCK), st, s, r);
 }

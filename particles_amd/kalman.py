@@ -139,6 +139,9 @@ class LinearGauss(MVLinearGauss):
     def PX(self, t, xp):
         return _gauss(self.rho * xp, self.sigmaX)
 
+    def upper_bound_log_pt(self, t):
+        return ssms.gauss_log_bound(self.sigmaX)
+
     def PY(self, t, xp, x):
         return _gauss(x, self.sigmaY)
 

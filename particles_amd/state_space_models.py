@@ -21,6 +21,12 @@ def _gauss(loc=0.0, scale=1.0):
     return dists.Normal(loc=loc, scale=scale)
 
 
+def gauss_log_bound(scale):
+    """log of the largest value of a N(., scale^2) density: the tight ``upper_bound_log_pt`` of a model whose
+    transition is Gaussian with a fixed scale."""
+    return -np.log(scale) - 0.5 * np.log(2.0 * np.pi)
+
+
 class StateSpaceModel:
     """Base class for state-space models (state_space_models.py:172-296): parameters are
     attributes (class-level ``default_params`` overridden by keyword arguments), the model is
@@ -48,6 +54,13 @@ class StateSpaceModel:
     def PY(self, t, xp, x):
         """Law of Y_t given X_{t-1} = xp and X_t = x."""
         raise self._undefined("PY")
+
+    def upper_bound_log_pt(self, t):
+        """log C_t of a constant with p_t(x_t | x_{t-1}) <= C_t for all x_{t-1}, x_t: what rejection-based
+        backward sampling divides by.  Any valid bound keeps the sampler exact; a looser one costs trials."""
+        raise NotImplementedError(
+            "%s does not define upper_bound_log_pt(t): it must return the log of a constant C_t with "
+            "p_t(x_t | x_{t-1}) <= C_t for every x_{t-1} and x_t" % type(self).__name__)
 
     def proposal0(self, data):
         raise self._undefined("proposal0")
@@ -114,6 +127,10 @@ class Bootstrap(FeynmanKac):
     def logpt(self, t, xp, x):
         """log-density of X_t = x given X_{t-1} = xp."""
         return self.ssm.PX(t, xp).logpdf(x)
+
+    def upper_bound_trans(self, t):
+        """log of an upper bound of the transition density of step t (state_space_models.py:345-346)."""
+        return self.ssm.upper_bound_log_pt(t)
 
     def _device_model(self):
         """Parameters of the fused device loop, or None.  The fused kernels implement the STOCK
@@ -209,6 +226,9 @@ class _AR1State(StateSpaceModel):
         _, persistence, sd = self._ar1_values()
         return sd / np.sqrt(1.0 - persistence ** 2)
 
+    def upper_bound_log_pt(self, t):
+        return gauss_log_bound(self._ar1_values()[2])
+
 
 class StochVol(_AR1State):
     r"""Univariate stochastic volatility model (state_space_models.py:446-473).
@@ -300,6 +320,9 @@ class Gordon_etal(StateSpaceModel):
     def PX(self, t, xp):
         pulled = self.b * xp + self.c * xp / (1.0 + xp ** 2)
         return _gauss(pulled + self._forcing(t), self.sigmaX)
+
+    def upper_bound_log_pt(self, t):
+        return gauss_log_bound(self.sigmaX)
 
     def PY(self, t, xp, x):
         return _gauss(self.a * x ** 2)
@@ -401,6 +424,9 @@ class ThetaLogistic(StateSpaceModel):
     def PX(self, t, xp):
         grown = xp + self.tau0                          # (the reference's association: (x + tau0) - tau1 exp(.))
         return _gauss(grown - self.tau1 * np.exp(self.tau2 * xp), self.sigmaX)
+
+    def upper_bound_log_pt(self, t):
+        return gauss_log_bound(self.sigmaX)
 
     def PY(self, t, xp, x):
         return _gauss(x, self.sigmaY)

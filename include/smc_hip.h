@@ -524,6 +524,36 @@ int smc_filter_backward_reject(smc_filter* f, int island, int64_t M, int64_t max
                                const double* u_host,
                                int64_t* idx_out_host, double* paths_out_host,
                                int64_t* nprops_out_host, int64_t* nexact_out_host);
+/* An additive function whose terms are polynomials of degree <= 2 in each argument, K <= 8 components:
+ * psi_0(x) = sum_j c0[k][j] x^j at t = 0, psi_t(xp, x) = sum_ij c[k][i][j] xp^i x^j at t >= 1. */
+typedef struct smc_addfunc {
+    int K;
+    double c0[8][3];
+    double c[8][3][3];
+} smc_addfunc;
+enum smc_online_method { SMC_ONLINE_NAIVE = 0, SMC_ONLINE_ON2 = 1, SMC_ONLINE_PARIS = 2 };
+/* On-line smoothing of an additive function (collectors.py:345-449 Online_smooth_naive / Online_smooth_ON2 / Paris),
+ * one call behind every step of a filter of the kinds smc_filter_backward_sample takes (any keep_history): the update
+ * of step t = (steps executed) - 1.  The caller owns the state between calls, all on the device: Phi_dev (N, K),
+ * Xprev_dev (N), lwprev_dev (N) -- in: Phi_{t-1}, X_{t-1}, lw_{t-1} (not read at t = 0); out: Phi_t, X_t, lw_t.
+ *   t = 0   Phi[n] = psi_0(X_0[n])
+ *   NAIVE   Phi_t[n] = Phi_{t-1}[a] + psi(X_{t-1}[a], X_t[n]), a = A_t[n] (n where step t did not resample)
+ *   ON2     Phi_t[n] = sum_m e_m (Phi_{t-1}[m] + psi(X_{t-1}[m], X_t[n])) / sum_m e_m, e_m = exp(l_m - max l),
+ *           l_m = lw_{t-1}[m] + log p_t(X_t[n] | X_{t-1}[m]); l_m = -inf or NaN weighs 0; no finite l_m: NaN
+ *   PARIS   Phi_t[n] = mean over r < n_paris of Phi_{t-1}[a] + psi(X_{t-1}[a], X_t[n]), a = As[n, r]: the hybrid of
+ *           smc_filter_backward_reject with N n_paris trajectories (trajectory j draws for target X_t[j / n_paris]),
+ *           proposals from W_{t-1}, acceptance iff log(u_acc) < log p_t - log_bound, at most max_trials trials (held to
+ *           2^24 - 1), then the exact draw.  u_prop_host / u_acc_host (max_trials, N n_paris), u_host (N n_paris): replay
+ *           tapes or NULL (Philox streams 4 and 3 keyed by `seed`, counters (j, t - 1, island, .)).  N n_paris < 2^31.
+ * then est_out_host[k] = sum_n W_t[n] Phi_t[n, k] with W_t as SMC_FIELD_W.  idx_out_host (N, n_paris) or NULL: As;
+ * nprop_out or NULL: trials made (PARIS, t >= 1; else 0).  Sums have a fixed order: the same bits from run to run.
+ * Reads the filter only.  SMC_ERR_INVALID: null arguments, K outside 1..8, unknown method, no step executed, SQMC
+ * filters, SVLEVERAGE, MVLINGAUSS, n_paris < 1, max_trials < 1. */
+int smc_filter_online_smooth(smc_filter* f, int island, int method, const smc_addfunc* psi,
+                             double* Phi_dev, double* Xprev_dev, double* lwprev_dev,
+                             int n_paris, int64_t max_trials, uint64_t seed, double log_bound,
+                             const double* u_prop_host, const double* u_acc_host, const double* u_host,
+                             int64_t* idx_out_host, int64_t* nprop_out, double* est_out_host);
 int smc_filter_info(smc_filter* f, double* bytes_per_particle_step,
                     int* kernels_per_step);
 /* Average duration (ms) of the step's two parts -- the propagate kernel ("move") and the

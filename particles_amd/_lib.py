@@ -27,6 +27,8 @@ FK_BOOTSTRAP, FK_GUIDED, FK_APF, FK_APF_BOOT = 0, 1, 2, 3
 FIELD_X, FIELD_XP, FIELD_A, FIELD_LW, FIELD_W = range(5)
 BACKWARD_ON2, BACKWARD_MCMC, BACKWARD_REJECT = 0, 1, 2
 REJECT_MAX_TRIALS = 2 ** 24 - 1
+ONLINE_NAIVE, ONLINE_ON2, ONLINE_PARIS = 0, 1, 2
+ADDFUNC_KMAX = 8
 SUMMARY_COLS = 5
 PARAM_STRIDE = 16
 
@@ -46,6 +48,10 @@ class SmcFilterOpts(ctypes.Structure):
                 ("rng_mode", ctypes.c_int32), ("use_graph", ctypes.c_int32),
                 ("island_offset", ctypes.c_int32), ("keep_history", ctypes.c_int32),
                 ("moments", ctypes.c_int32), ("flags", ctypes.c_int32)]
+
+
+class SmcAddFunc(ctypes.Structure):
+    _fields_ = [("K", c_int), ("c0", c_dbl * 3 * 8), ("c", c_dbl * 3 * 3 * 8)]
 
 
 FLAG_COLLAPSED_PROPOSAL = 1
@@ -166,6 +172,8 @@ SIGNATURES = {
                                            P(c_dbl), P(c_i64), P(c_dbl)]),
     "smc_filter_backward_reject": (c_int, [c_vp, c_int, c_i64, c_i64, c_u64, P(c_dbl), P(c_i64), P(c_dbl), P(c_dbl),
                                            P(c_dbl), P(c_dbl), P(c_i64), P(c_dbl), P(c_i64), P(c_i64)]),
+    "smc_filter_online_smooth": (c_int, [c_vp, c_int, c_int, P(SmcAddFunc), c_vp, c_vp, c_vp, c_int, c_i64, c_u64, c_dbl,
+                                         P(c_dbl), P(c_dbl), P(c_dbl), P(c_i64), P(c_i64), P(c_dbl)]),
     "smc_filter_spacings": (c_int, [c_vp, c_i64, c_int, P(c_dbl)]),
     "smc_filter_info": (c_int, [c_vp, P(c_dbl), P(c_int)]),
     "smc_filter_profile": (c_int, [c_vp, c_int]),

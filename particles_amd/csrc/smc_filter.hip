@@ -10,6 +10,7 @@
 #include "smc_filter_wide.h"
 #include "smc_filter_strict.h"
 #include "smc_smooth.h"
+#include "smc_online.h"
 
 // ---------------------------------------------------------------------------
 // host side
@@ -1974,7 +1975,7 @@ int smc_filter_one_trajectory(smc_filter* f, int island, int64_t n_last, double*
             return SMC_ERR_INVALID;                            \
         }                                                      \
     } while (0)
-static int sm_check_filter(const char* who, smc_filter* f, int island, const void* idx_out_host)
+static int sm_check_filter(const char* who, smc_filter* f, int island, const void* idx_out_host, bool whole_history = true)
 {
     SM_REQUIRE(who, f && idx_out_host, "null argument");
     SM_REQUIRE(who, !f->plan.sqmc(), "SQMC filters are not supported (backward_sampling_qmc is a different algorithm)");
@@ -1982,7 +1983,7 @@ static int sm_check_filter(const char* who, smc_filter* f, int island, const voi
     SM_REQUIRE(who, f->kind != SMC_MODEL_MVLINGAUSS, "model kind MVLINGAUSS is not supported: univariate models only");
     SM_REQUIRE(who, f->kind == SMC_MODEL_LINGAUSS || f->kind == SMC_MODEL_STOCHVOL || f->kind == SMC_MODEL_GORDON ||
                f->kind == SMC_MODEL_THETALOGISTIC || f->kind == SMC_MODEL_DISCRETECOX, "model kind is not supported");
-    SM_REQUIRE(who, f->a.hist == 1, "the filter was created without a whole history (keep_history = 1)");
+    SM_REQUIRE(who, !whole_history || f->a.hist == 1, "the filter was created without a whole history (keep_history = 1)");
     SM_REQUIRE(who, island >= 0 && island < f->a.n_islands, "island out of range");
     return SMC_OK;
 }
@@ -2020,16 +2021,19 @@ static const double* sm_rows(smc_filter* f, int island)
 {
     return f->a.summ + (size_t)island * (f->a.T + 1) * SUMM_STRIDE;
 }
-// cdf = the integer CDF of W_step
-static void sm_weights_cdf(smc_filter* f, int island, i64 step, const SmArgs& s, u64* tot, u64* cdf)
+// cdf = the integer CDF of the weights (lw, row) normalise to
+static void sm_cdf_of(smc_filter* f, const double* lw, const double* row, const SmArgs& s, u64* tot, u64* cdf)
 {
     const i64 N = f->a.N;
     const unsigned nch = (unsigned)((N + SM_CHUNK - 1) / SM_CHUNK);
-    const double* lw = f_lw(f->a, step) + (size_t)island * N;
-    const double* row = sm_rows(f, island) + (size_t)step * SUMM_STRIDE;
     hipStream_t st = f->ctx->stream;
     SMC_LAUNCH(k_sm_cdf_totals, dim3(nch), dim3(SMC_BLOCK), st, lw, row, N, s.kform, s.shift, tot);
     SMC_LAUNCH(k_sm_cdf_scan, dim3(nch), dim3(SMC_BLOCK), st, lw, row, N, s.kform, s.shift, (const u64*)tot, cdf);
+}
+// cdf = the integer CDF of W_step
+static void sm_weights_cdf(smc_filter* f, int island, i64 step, const SmArgs& s, u64* tot, u64* cdf)
+{
+    sm_cdf_of(f, f_lw(f->a, step) + (size_t)island * f->a.N, sm_rows(f, island) + (size_t)step * SUMM_STRIDE, s, tot, cdf);
 }
 // last row: M iid draws from W_{t-1} (smoothing.py:278-281), or the caller's indices
 static int sm_last_row(smc_filter* f, int island, SmArgs& s, i64* idx, const int64_t* idx_last_host, const double* d_ulast,
@@ -2210,6 +2214,149 @@ int smc_filter_backward_reject(smc_filter* f, int island, int64_t M, int64_t max
         if (nprops_out_host) nprops_out_host[b] = (int64_t)counts[b * SM_CTR_STRIDE + SM_CTR_NPROPS];
         if (nexact_out_host) nexact_out_host[b] = (int64_t)counts[b * SM_CTR_STRIDE + SM_CTR_NEXACT];
     }
+    return SMC_OK;
+}
+
+// On-line smoothing (smc_online.h): one update behind the step just run.  Stateless: Phi, X_{t-1} and lw_{t-1} are the
+// caller's device arrays, everything else is read from the filter's current step or lives in pool workspaces for the
+// duration of the call.  One synchronisation: the download of the K estimates (and what else was asked for).
+int smc_filter_online_smooth(smc_filter* f, int island, int method, const smc_addfunc* psi_host,
+                             double* Phi_dev, double* Xprev_dev, double* lwprev_dev,
+                             int n_paris, int64_t max_trials, uint64_t seed, double log_bound,
+                             const double* u_prop_host, const double* u_acc_host, const double* u_host,
+                             int64_t* idx_out_host, int64_t* nprop_out, double* est_out_host)
+{
+    if (f) { (void)hipSetDevice(f->ctx->device); flush_rows(f); }
+    int rc = sm_check_filter(__func__, f, island, est_out_host, false);
+    if (rc != SMC_OK) return rc;
+    SMC_REQUIRE(psi_host && Phi_dev && Xprev_dev && lwprev_dev, "null argument");
+    SMC_REQUIRE(psi_host->K >= 1 && psi_host->K <= OS_KMAX, "K must be 1 .. 8");
+    SMC_REQUIRE(method == SMC_ONLINE_NAIVE || method == SMC_ONLINE_ON2 || method == SMC_ONLINE_PARIS, "unknown method");
+    if ((rc = sm_check_steps(__func__, f)) != SMC_OK) return rc;
+    const bool paris = method == SMC_ONLINE_PARIS;
+    const i64 N = f->a.N, t = f->t_host - 1;
+    if (paris) {
+        SMC_REQUIRE(n_paris >= 1, "n_paris must be at least 1");
+        SMC_REQUIRE(max_trials >= 1, "max_trials must be at least 1");
+        SMC_REQUIRE(N * (i64)n_paris < ((i64)1 << 31), "N n_paris must stay below 2^31");
+        if (max_trials > SM_REJ_MAX_TRIALS) max_trials = SM_REJ_MAX_TRIALS;
+    }
+    OsPsi psi{};
+    const int K = psi.K = psi_host->K;
+    memcpy(psi.c0, psi_host->c0, sizeof psi.c0);
+    memcpy(psi.c, psi_host->c, sizeof psi.c);
+    hipStream_t st = f->ctx->stream;
+    SmPool pool(f->ctx);
+    const unsigned nblk = (unsigned)((N + SMC_BLOCK - 1) / SMC_BLOCK);
+    const int nest = (int)((N + OS_EST_CHUNK - 1) / OS_EST_CHUNK);
+    const double* X = f_X(f->a, t) + (size_t)island * N;
+    const double* lw = f_lw(f->a, t) + (size_t)island * N;
+    const double* rows = sm_rows(f, island);
+    const double* row = rows + (size_t)t * SUMM_STRIDE;
+    double *est = nullptr, *epart = nullptr;
+    rc = pool.get((size_t)OS_KMAX, &est);
+    if (rc == SMC_OK) rc = pool.get((size_t)nest * OS_KMAX, &epart);
+    if (rc != SMC_OK) return rc;
+    const i64 M = paris ? N * n_paris : 0;
+    i64* idx = nullptr;
+    u64* ctr = nullptr;
+    if (t == 0) {
+        SMC_LAUNCH(k_os_init, dim3(nblk), dim3(SMC_BLOCK), st, psi, X, N, Phi_dev);
+    } else {
+        SmArgs s = sm_args(f, island, M, seed, nullptr);
+        s.t = (u32)(t - 1);
+        s.Xt = Xprev_dev; s.lwt = lwprev_dev; s.Xn = X;
+        s.An = f_A(f->a, t) + (size_t)island * N;
+        s.rowt = rows + (size_t)(t - 1) * SUMM_STRIDE;
+        s.rown = row;
+        s.aux = f->a.aux ? f->a.aux + t : nullptr;
+        double* Phi_new = nullptr;
+        if (method == SMC_ONLINE_ON2) {
+            const int nslices = os_slices(N);
+            const int KP = K == 1 ? 1 : K <= 4 ? 4 : 8;
+            double *loc = nullptr, *part = nullptr;
+            rc = pool.get((size_t)N, &loc);
+            if (rc == SMC_OK) rc = pool.get((size_t)nslices * N * OS_PART(KP), &part);
+            if (rc != SMC_OK) return rc;
+            int slot = 1;
+            switch (f->kind) {
+            case SMC_MODEL_LINGAUSS: os_launch_loc<SMC_MODEL_LINGAUSS>(st, s, loc); slot = sm_scale_slot<SMC_MODEL_LINGAUSS>(); break;
+            case SMC_MODEL_STOCHVOL: os_launch_loc<SMC_MODEL_STOCHVOL>(st, s, loc); slot = sm_scale_slot<SMC_MODEL_STOCHVOL>(); break;
+            case SMC_MODEL_GORDON: os_launch_loc<SMC_MODEL_GORDON>(st, s, loc); slot = sm_scale_slot<SMC_MODEL_GORDON>(); break;
+            case SMC_MODEL_THETALOGISTIC:
+                os_launch_loc<SMC_MODEL_THETALOGISTIC>(st, s, loc); slot = sm_scale_slot<SMC_MODEL_THETALOGISTIC>(); break;
+            default: os_launch_loc<SMC_MODEL_DISCRETECOX>(st, s, loc); slot = sm_scale_slot<SMC_MODEL_DISCRETECOX>(); break;
+            }
+            OsOn2 o{};
+            o.X = X; o.Xprev = Xprev_dev; o.lwprev = lwprev_dev; o.loc = loc; o.Phi = Phi_dev;
+            o.part = part; o.p = s.p; o.slot = slot; o.N = N; o.K = K;
+            const i64 ntile = (N + OS_TILE - 1) / OS_TILE;
+            o.per_slice = ((ntile + nslices - 1) / nslices) * OS_TILE;
+            const int used = (int)((N + o.per_slice - 1) / o.per_slice);            // (no empty slice is launched or merged)
+            // (the merge reads every partial before it writes a target's Phi, and k_os_on2 is done: Phi_dev in place)
+            if (KP == 1) os_launch_on2<1>(st, o, used, psi, Phi_dev);
+            else if (KP == 4) os_launch_on2<4>(st, o, used, psi, Phi_dev);
+            else os_launch_on2<8>(st, o, used, psi, Phi_dev);
+        } else {
+            if ((rc = pool.get((size_t)N * K, &Phi_new)) != SMC_OK) return rc;
+            if (paris) {
+                const unsigned nch = (unsigned)((N + SM_CHUNK - 1) / SM_CHUNK);
+                u64 *cdf = nullptr, *tot = nullptr;
+                u32 *listA = nullptr, *listB = nullptr;
+                i64* targets = nullptr;
+                double *d_u = nullptr, *d_uprop = nullptr, *d_uacc = nullptr, *d_logC = nullptr;
+                rc = pool.get((size_t)N, &cdf);
+                if (rc == SMC_OK) rc = pool.get((size_t)nch, &tot);
+                if (rc == SMC_OK) rc = pool.get((size_t)SM_CTR_STRIDE, &ctr);
+                if (rc == SMC_OK) rc = pool.get((size_t)M, &listA);
+                if (rc == SMC_OK) rc = pool.get((size_t)M, &listB);
+                if (rc == SMC_OK) rc = pool.get((size_t)M, &targets);
+                if (rc == SMC_OK) rc = pool.get((size_t)M, &idx);
+                if (rc == SMC_OK) rc = pool.upload(&log_bound, 1, &d_logC);
+                if (rc == SMC_OK) rc = pool.upload(u_host, (size_t)M, &d_u);
+                if (rc == SMC_OK) rc = pool.upload(u_prop_host, (size_t)max_trials * M, &d_uprop);
+                if (rc == SMC_OK) rc = pool.upload(u_acc_host, (size_t)max_trials * M, &d_uacc);
+                if (rc != SMC_OK) return rc;
+                SMC_HIP_CHECK(hipMemsetAsync(idx, 0, (size_t)M * 8, st));              // (every index a kernel reads is in range)
+                SMC_HIP_CHECK(hipMemsetAsync(ctr, 0, SM_CTR_STRIDE * 8, st));
+                SMC_LAUNCH(k_os_targets, dim3((unsigned)((M + SMC_BLOCK - 1) / SMC_BLOCK)), dim3(SMC_BLOCK), st, M, n_paris, targets);
+                s.cdf = cdf;
+                sm_cdf_of(f, lwprev_dev, s.rowt, s, tot, cdf);
+                s.u = d_u;
+                s.idx_next = targets;
+                s.idx_out = idx;
+                SmRej r{};
+                r.listA = listA; r.listB = listB;
+                r.max_trials = max_trials;
+                r.solo = max_trials < sm_reject_solo_trials() ? max_trials : sm_reject_solo_trials();
+                r.u_prop = d_uprop; r.u_acc = d_uacc;
+                r.logC = d_logC;
+                r.ctr = ctr;
+                switch (f->kind) {
+                case SMC_MODEL_LINGAUSS: sm_launch_reject<SMC_MODEL_LINGAUSS>(st, s, r); break;
+                case SMC_MODEL_STOCHVOL: sm_launch_reject<SMC_MODEL_STOCHVOL>(st, s, r); break;
+                case SMC_MODEL_GORDON: sm_launch_reject<SMC_MODEL_GORDON>(st, s, r); break;
+                case SMC_MODEL_THETALOGISTIC: sm_launch_reject<SMC_MODEL_THETALOGISTIC>(st, s, r); break;
+                default: sm_launch_reject<SMC_MODEL_DISCRETECOX>(st, s, r); break;
+                }
+            }
+            SMC_LAUNCH(k_os_gather, dim3(nblk), dim3(SMC_BLOCK), st, psi, X, (const double*)Xprev_dev, (const double*)Phi_dev,
+                       s.An, row, (const i64*)idx, paris ? n_paris : 0, N, Phi_new);
+            SMC_HIP_CHECK(hipMemcpyAsync(Phi_dev, Phi_new, (size_t)N * K * 8, hipMemcpyDeviceToDevice, st));
+        }
+    }
+    SMC_LAUNCH(k_os_est_partials, dim3((unsigned)nest), dim3(SMC_BLOCK), st, lw, row, (const double*)Phi_dev, N, K,
+               f->plan.two_level ? 1 : 0, epart);
+    SMC_LAUNCH(k_os_est_final, dim3(1), dim3(64), st, (const double*)epart, nest, K, est);
+    SMC_LAUNCH_CHECK();
+    SMC_HIP_CHECK(hipMemcpyAsync(Xprev_dev, X, (size_t)N * 8, hipMemcpyDeviceToDevice, st));
+    SMC_HIP_CHECK(hipMemcpyAsync(lwprev_dev, lw, (size_t)N * 8, hipMemcpyDeviceToDevice, st));
+    u64 counts[SM_CTR_STRIDE] = {0, 0, 0, 0};
+    if (ctr && nprop_out) SMC_HIP_CHECK(hipMemcpyAsync(counts, ctr, sizeof counts, hipMemcpyDeviceToHost, st));
+    if (idx && idx_out_host) SMC_HIP_CHECK(hipMemcpyAsync(idx_out_host, idx, (size_t)M * 8, hipMemcpyDeviceToHost, st));
+    SMC_HIP_CHECK(hipMemcpyAsync(est_out_host, est, (size_t)K * 8, hipMemcpyDeviceToHost, st));
+    SMC_HIP_CHECK(hipStreamSynchronize(st));
+    if (nprop_out) *nprop_out = (int64_t)counts[SM_CTR_NPROPS];
     return SMC_OK;
 }
 

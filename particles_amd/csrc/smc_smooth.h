@@ -91,7 +91,7 @@ __device__ __forceinline__ double sm_W(double l, double m, double rs, int kform)
     return smc_scale_pk(p, k, m) * rs;
 }
 template <int KIND>
-__device__ __forceinline__ int sm_scale_slot()
+__host__ __device__ __forceinline__ int sm_scale_slot()
 {
     return (KIND == SMC_MODEL_STOCHVOL || KIND == SMC_MODEL_SVLEVERAGE || KIND == SMC_MODEL_DISCRETECOX) ? 2 : 1;
 }

@@ -27,6 +27,49 @@ def gauss_log_bound(scale):
     return -np.log(scale) - 0.5 * np.log(2.0 * np.pi)
 
 
+class QuadAddFunc:
+    """An additive function in closed form, so that the on-line smoothing collectors can evaluate it on the device:
+
+        psi_0(x)     = sum_j  c0[k, j]   x**j                j    in 0..2
+        psi_t(xp, x) = sum_ij c[k, i, j] xp**i x**j          i, j in 0..2,  t >= 1;   k < K <= 8
+
+    ``c0`` is (K, 3) and ``c`` (K, 3, 3); (3,) and (3, 3) mean K = 1.  This covers ``x**2`` / ``(xp - x)**2`` and
+    every sufficient statistic of the Gaussian AR(1) family (``x``, ``x**2``, ``xp * x``, ``xp**2``).  A model uses it
+    as a class or instance attribute: ``add_func = QuadAddFunc(c0, c)``."""
+
+    def __init__(self, c0, c):
+        c0, c = np.array(c0, dtype=np.float64), np.array(c, dtype=np.float64)
+        self.scalar = c0.ndim == 1 and c.ndim == 2
+        if self.scalar:
+            c0, c = c0[None], c[None]
+        if c0.ndim != 2 or c.ndim != 3 or c0.shape[1:] != (3,) or c.shape[1:] != (3, 3) or len(c0) != len(c):
+            raise ValueError("QuadAddFunc: c0 must be (K, 3) and c (K, 3, 3) (or (3,) and (3, 3))")
+        if not 1 <= len(c) <= _lib.ADDFUNC_KMAX:
+            raise ValueError("QuadAddFunc: K must be 1 .. %d" % _lib.ADDFUNC_KMAX)
+        self.c0, self.c, self.K = c0, c, len(c)
+
+    def __call__(self, t, xp, x):
+        """NumPy; ``xp`` and ``x`` broadcast against each other.  Returns (...) for K = 1 given as (3,), (3, 3),
+        else (..., K)."""
+        x = np.asarray(x, dtype=np.float64)
+        if t == 0 or xp is None:
+            out = sum(self.c0[:, j] * (x ** j)[..., None] for j in range(3))
+        else:
+            xp = np.asarray(xp, dtype=np.float64)
+            out = sum(self.c[:, i, j] * ((xp ** i) * (x ** j))[..., None] for i in range(3) for j in range(3))
+        return out[..., 0] if self.scalar else out
+
+    def _struct(self):
+        f = _lib.SmcAddFunc()
+        f.K = self.K
+        for k in range(self.K):
+            for i in range(3):
+                f.c0[k][i] = self.c0[k, i]
+                for j in range(3):
+                    f.c[k][i][j] = self.c[k, i, j]
+        return f
+
+
 class StateSpaceModel:
     """Base class for state-space models (state_space_models.py:172-296): parameters are
     attributes (class-level ``default_params`` overridden by keyword arguments), the model is
@@ -61,6 +104,10 @@ class StateSpaceModel:
         raise NotImplementedError(
             "%s does not define upper_bound_log_pt(t): it must return the log of a constant C_t with "
             "p_t(x_t | x_{t-1}) <= C_t for every x_{t-1} and x_t" % type(self).__name__)
+
+    def add_func(self, t, xp, x):
+        """Additive function psi_t(xp, x) of on-line smoothing (psi_0(x) at t = 0, where xp is None)."""
+        raise self._undefined("add_func")
 
     def proposal0(self, data):
         raise self._undefined("proposal0")
@@ -131,6 +178,9 @@ class Bootstrap(FeynmanKac):
     def upper_bound_trans(self, t):
         """log of an upper bound of the transition density of step t (state_space_models.py:345-346)."""
         return self.ssm.upper_bound_log_pt(t)
+
+    def add_func(self, t, xp, x):
+        return self.ssm.add_func(t, xp, x)
 
     def _device_model(self):
         """Parameters of the fused device loop, or None.  The fused kernels implement the STOCK

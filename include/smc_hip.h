@@ -554,6 +554,40 @@ int smc_filter_online_smooth(smc_filter* f, int island, int method, const smc_ad
                              int n_paris, int64_t max_trials, uint64_t seed, double log_bound,
                              const double* u_prop_host, const double* u_acc_host, const double* u_host,
                              int64_t* idx_out_host, int64_t* nprop_out, double* est_out_host);
+enum smc_two_filter_method { SMC_TWOFILTER_ON2 = 0, SMC_TWOFILTER_ON = 1 };
+/* Two-filter smoothing (smoothing.py:487-575, ParticleHistory.two_filter_smoothing; the O(N) form is Fearnhead, Wyncoll &
+ * Tawn 2010): the expectation of phi(X_t, X_{t+1}) from a forward filter f and an information filter `info` (the same
+ * model run on the reversed data), both keep_history == 1, both on ONE context.  With T the steps f has run, 0 <= t <= T - 2
+ * and ti = T - 2 - t a step `info` has run:
+ *   x_n = X_t[n] of f (n < N_f), x'_m = X_ti[m] of info (m < N_i; N_f != N_i is allowed),
+ *   lwi_m = lw_ti[m] of info - loggamma(x'_m), loggamma(x) = loggamma3[0] + loggamma3[1] x + loggamma3[2] x^2,
+ *   log p = f's transition log p_{t+1}(x' | x), its island's parameters (nothing of info but X_ti, lw_ti is read),
+ *   phi_k(x, x') = sum_ij phi->c[k][i][j] x^i x'^j, k < phi->K <= 8 (phi->c0 is not read).
+ * SMC_TWOFILTER_ON2: est[k] = sum_nm w_nm phi_k(x_n, x'_m) / sum_nm w_nm, w_nm = exp(lw_t[n] + lwi_m + log p(x'_m | x_n) - c):
+ *   an all-pairs launch, one target x'_m per thread.  A constant common to all pairs (the density's -log(scale sqrt(2 pi)),
+ *   the reference's upb) cancels and is not formed.  A -inf or NaN exponent weighs 0; no finite exponent at all: NaN.
+ *   This is the reference's value, not its rounding order -- and in the reference a NaN exponent poisons the sum.
+ *   modif_*, npairs, seed, u_*, idx_* are not read.
+ * SMC_TWOFILTER_ON: npairs pairs (J_j, I_j), 1 <= npairs < 2^31.  J_j = the inverse of u_fwd[j] in the integer CDF (DESIGN
+ *   section 6) of W_t as SMC_FIELD_W -- with modif_forward_host (N_f): of exp(lw_t[n] + modif_forward[n] - max); I_j = the
+ *   inverse of u_info[j] in the integer CDF of exp(lwi_m + modif_info[m] - max).  lo_j = log p(x'_I | x_J) -
+ *   modif_forward[J] - modif_info[I], Om = exp(lo - max) / sum: est[k] = sum_j Om_j phi_k(x_J, x'_I), ess = 1 / sum Om^2.
+ *   u_fwd_host / u_info_host (npairs): replay tapes or NULL (Philox stream 5, key `seed`, counter (j, t, island, 5): word
+ *   x01 -> u_fwd, word x23 -> u_info, both [0, 1)).  idx_fwd_host / idx_info_host (npairs), given together: these pairs
+ *   instead of draws.  idx_*_out_host (npairs) or NULL: the pairs used.  The pairs are iid in draw order; the reference
+ *   pairs two SORTED multinomial samples position by position -- another coupling of the same two marginals.
+ * est_out_host (K); ess_out_host: one word or NULL (meaningful for ON).  Sums have a fixed order: the same bits from run to
+ * run.  Reads both filters only.  SMC_ERR_INVALID: null f, info, phi, loggamma3, est_out_host; filters on different
+ * contexts; f SVLEVERAGE, MVLINGAUSS or SQMC; info multivariate or SQMC; either keep_history != 1; t outside 0 .. T - 2;
+ * ti not run by info; an island out of range; K outside 1..8; unknown method; ON: npairs < 1, a given index out of range. */
+int smc_filter_two_filter(smc_filter* f, int island, smc_filter* info, int island_info, int64_t t, int method,
+                          const smc_addfunc* phi, const double* loggamma3,
+                          const double* modif_forward_host, const double* modif_info_host,
+                          int64_t npairs, uint64_t seed,
+                          const double* u_fwd_host, const double* u_info_host,
+                          const int64_t* idx_fwd_host, const int64_t* idx_info_host,
+                          int64_t* idx_fwd_out_host, int64_t* idx_info_out_host,
+                          double* est_out_host, double* ess_out_host);
 int smc_filter_info(smc_filter* f, double* bytes_per_particle_step,
                     int* kernels_per_step);
 /* Average duration (ms) of the step's two parts -- the propagate kernel ("move") and the

@@ -28,6 +28,7 @@ FIELD_X, FIELD_XP, FIELD_A, FIELD_LW, FIELD_W = range(5)
 BACKWARD_ON2, BACKWARD_MCMC, BACKWARD_REJECT = 0, 1, 2
 REJECT_MAX_TRIALS = 2 ** 24 - 1
 ONLINE_NAIVE, ONLINE_ON2, ONLINE_PARIS = 0, 1, 2
+TWOFILTER_ON2, TWOFILTER_ON = 0, 1
 ADDFUNC_KMAX = 8
 SUMMARY_COLS = 5
 PARAM_STRIDE = 16
@@ -174,6 +175,9 @@ SIGNATURES = {
                                            P(c_dbl), P(c_dbl), P(c_i64), P(c_dbl), P(c_i64), P(c_i64)]),
     "smc_filter_online_smooth": (c_int, [c_vp, c_int, c_int, P(SmcAddFunc), c_vp, c_vp, c_vp, c_int, c_i64, c_u64, c_dbl,
                                          P(c_dbl), P(c_dbl), P(c_dbl), P(c_i64), P(c_i64), P(c_dbl)]),
+    "smc_filter_two_filter": (c_int, [c_vp, c_int, c_vp, c_int, c_i64, c_int, P(SmcAddFunc), P(c_dbl), P(c_dbl), P(c_dbl),
+                                      c_i64, c_u64, P(c_dbl), P(c_dbl), P(c_i64), P(c_i64), P(c_i64), P(c_i64), P(c_dbl),
+                                      P(c_dbl)]),
     "smc_filter_spacings": (c_int, [c_vp, c_i64, c_int, P(c_dbl)]),
     "smc_filter_info": (c_int, [c_vp, P(c_dbl), P(c_int)]),
     "smc_filter_profile": (c_int, [c_vp, c_int]),

@@ -360,6 +360,147 @@ class Paris(_OnlineSmoother):
         return Phi / R
 
 
+
+# ---- two-filter smoothing (smoothing.py:487-575) -----------------------------
+
+_TWO_FILTER_T_ERR = "two-filter smoothing: t must be in range 0,...,T-2"
+_TWO_FILTER_TAPES = {"u_fwd": np.float64, "u_info": np.float64, "idx_fwd": np.int64, "idx_info": np.int64}
+
+
+def _two_filter_replay(replay, P):
+    """The replay dict of ``two_filter_smoothing`` as contiguous arrays (None where absent)."""
+    replay = dict(replay or {})
+    unknown = set(replay) - set(_TWO_FILTER_TAPES)
+    if unknown:
+        raise ValueError("two-filter smoothing: unknown replay tape(s) %s" % sorted(unknown))
+    tapes = {}
+    for k, dt in _TWO_FILTER_TAPES.items():
+        if replay.get(k) is None:
+            tapes[k] = None
+            continue
+        a = np.ascontiguousarray(replay[k], dtype=dt)
+        if a.shape != (P,):
+            raise ValueError("two-filter smoothing: replay[%r] has shape %s, expected %s" % (k, a.shape, (P,)))
+        tapes[k] = a
+    if (tapes["idx_fwd"] is None) != (tapes["idx_info"] is None):
+        raise ValueError("two-filter smoothing: replay['idx_fwd'] and replay['idx_info'] are given together")
+    return tapes
+
+
+def _two_filter_phi(phi):
+    """``phi(x, xf)`` of a ``QuadAddFunc``: its t >= 1 form, psi_t(xp, x) with xp = x and x = xf."""
+    from .state_space_models import QuadAddFunc
+    return (lambda x, xf: phi(1, x, xf)) if isinstance(phi, QuadAddFunc) else phi
+
+
+def _inverse_cdf_draws(W, u):
+    """Indices of the uniforms u in the cumulative sums of the weights W; a weightless particle is never drawn."""
+    W = np.where(np.isnan(W), 0.0, W)
+    cs = np.cumsum(W)
+    top = int(np.flatnonzero(W > 0)[-1]) if cs[-1] > 0 else len(W) - 1
+    return np.minimum(np.searchsorted(cs, u * cs[-1], side="right"), top).astype(np.int64)
+
+
+def _two_filter_numpy(hist, t, info, phi, loggamma, linear_cost, return_ess, modif_forward, modif_info, npairs, seed,
+                      replay, return_idx):
+    """The NumPy route of ``two_filter_smoothing``: the two estimators on arrays read through ``hist.X[...]`` and
+    ``hist.wgts[...]``, any callable ``phi(x, xf)`` and ``loggamma(x)``, ``fk.logpt`` on flat pair arrays (model code
+    is elementwise over particles).  The O(N^2) form goes over the information filter's particles in chunks of at most
+    ``_ON2_CHUNK_ELEMS`` pairs on one running maximum: never an N x N array.  A bound common to all pairs (the
+    reference's ``upper_bound_trans``) cancels, so none is asked for."""
+    T = hist.T
+    if t < 0 or t >= T - 1:
+        raise ValueError(_TWO_FILTER_T_ERR)
+    ti = T - 2 - t
+    fk = hist.fk
+    phi = _two_filter_phi(phi)
+    X, wf = np.asarray(hist.X[t]), hist.wgts[t]
+    Xi = np.asarray(info.hist.X[ti])
+    lw = np.asarray(wf.lw, dtype=np.float64)
+    lwi = np.asarray(info.hist.wgts[ti].lw, dtype=np.float64) - np.asarray(loggamma(Xi), dtype=np.float64)
+    Nf, Ni = len(X), len(Xi)
+    if not linear_cost:
+        G, A, B = -np.inf, 0.0, 0.0
+        step = max(1, _ON2_CHUNK_ELEMS // Nf)
+        for m0 in range(0, Ni, step):
+            xs = Xi[m0:m0 + step]
+            c = len(xs)
+            XP, XT = np.tile(X, (c,) + (1,) * (X.ndim - 1)), np.repeat(xs, Nf, axis=0)
+            l = np.asarray(fk.logpt(t + 1, XP, XT), dtype=np.float64).reshape(c, Nf) + lw[None, :] + lwi[m0:m0 + step, None]
+            l = np.where(np.isnan(l), -np.inf, l)
+            mx = l.max()
+            if not mx > -np.inf:
+                continue
+            if mx > G:
+                sc = np.exp(G - mx) if G > -np.inf else 0.0
+                A, B, G = A * sc, B * sc, mx
+            e = np.exp(l - G)
+            ph = np.asarray(phi(XP, XT), dtype=np.float64)
+            ph = ph.reshape((c, Nf) + ph.shape[1:])
+            ph = np.where((e > 0).reshape((c, Nf) + (1,) * (ph.ndim - 2)), ph, 0.0)
+            A = A + e.sum()
+            B = B + np.tensordot(e, ph, axes=([0, 1], [0, 1]))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            est = np.asarray(B, dtype=np.float64) / A if A > 0 else np.asarray(B, dtype=np.float64) * np.nan
+        est = est[()] if np.ndim(est) == 0 else est
+        # (the O(N^2) form has no ESS in the reference either: return_ess is the O(N) form's)
+        return est
+    P = int(Nf if npairs is None else npairs)
+    if P < 1:
+        raise ValueError("two-filter smoothing: npairs must be at least 1")
+    tapes = _two_filter_replay(replay, P)
+    mf = None if modif_forward is None else np.asarray(modif_forward, dtype=np.float64)
+    mi = None if modif_info is None else np.asarray(modif_info, dtype=np.float64)
+    if tapes["idx_fwd"] is not None:
+        J, I = tapes["idx_fwd"], tapes["idx_info"]
+        if J.min() < 0 or J.max() >= Nf or I.min() < 0 or I.max() >= Ni:
+            raise ValueError("two-filter smoothing: pair index out of range")
+    else:
+        rng = np.random.default_rng(seed)
+        u_f = tapes["u_fwd"] if tapes["u_fwd"] is not None else rng.random(P)
+        u_i = tapes["u_info"] if tapes["u_info"] is not None else rng.random(P)
+        W = np.asarray(wf.W) if mf is None else _exp_and_normalise_cols(lw + mf)
+        J = _inverse_cdf_draws(W, u_f)
+        I = _inverse_cdf_draws(_exp_and_normalise_cols(lwi if mi is None else lwi + mi), u_i)
+    lo = np.asarray(fk.logpt(t + 1, X[J], Xi[I]), dtype=np.float64)
+    if mf is not None:
+        lo = lo - mf[J]
+    if mi is not None:
+        lo = lo - mi[I]
+    Om = _exp_and_normalise_cols(lo)
+    est = np.average(np.asarray(phi(X[J], Xi[I]), dtype=np.float64), axis=0, weights=Om)
+    out = (est, 1.0 / np.sum(Om ** 2)) if return_ess else (est,)
+    if return_idx:
+        out = out + (J, I)
+    return out[0] if len(out) == 1 else out
+
+
+_TWO_FILTER_DOC = """Two-filter smoothing (smoothing.py:487-575): the smoothing expectation of ``phi(X_t, X_{t+1})`` from this
+        (forward) filter's history and the history of ``info``, the information filter -- the same model run on the
+        reversed data under the pseudo-prior ``gamma``.  The first eight parameters are the reference's.
+
+        t : 0 <= t <= T - 2
+        info : the information filter (an ``SMC`` object run with ``store_history=True``); step ``T - 2 - t`` of it is read
+        phi : ``phi(x, xf)`` of the forward particle and the information filter's; a ``QuadAddFunc`` stands for its
+            t >= 1 form ``psi_t(xp, x)`` with xp = x and x = xf
+        loggamma : ``loggamma(xf)``, the log-density of the pseudo-prior; ``QuadLogGamma`` in closed form
+        linear_cost : the O(N) estimator (Fearnhead, Wyncoll & Tawn 2010) instead of the O(N^2) double sum
+        return_ess : O(N) form: return ``(est, ess)``, ess = 1 / sum Om^2 of the pairs' weights
+        modif_forward, modif_info : (N_f), (N_i) log-modifiers of the two sampling weights, O(N) form only (silently
+            unused otherwise, as in the reference)
+        npairs : pairs of the O(N) form; None: N of the forward filter (the reference draws N)
+        seed, replay, return_idx : the O(N) draws: a key (Philox stream 5, counter (j, t, island, 5) on the device;
+            NumPy's generator on the host route), or a dict with uniforms ``u_fwd``, ``u_info`` (npairs,) or given pairs
+            ``idx_fwd``, ``idx_info`` (npairs,) int64; ``return_idx`` appends the pairs ``(J, I)`` to the result
+
+        The pairs are iid, in draw order.  The reference draws I and J with ``rs.multinomial``, which returns each
+        SORTED, and pairs them position by position: that is another coupling of the same two marginals -- both
+        estimators are consistent, their values differ draw by draw.  Unlike the reference no ``upper_bound_log_pt`` is
+        needed: a bound common to all pairs cancels.  A -inf or NaN pair weight counts as 0 (in the reference's O(N^2)
+        loop a NaN poisons the sum).
+
+        Returns a scalar for a scalar ``phi``, else (K,)."""
+
 # ---- history containers (smoothing.py:141-255) -----------------------------
 
 def generate_hist_obj(option, smc):
@@ -433,6 +574,15 @@ class ParticleHistory(RollingParticleHistory):
 
     def backward_sampling_reject(self, M, max_trials=None, **kw):
         return self.backward_sampling_ON2(M, **kw)
+
+
+    def two_filter_smoothing(self, t, info, phi, loggamma, linear_cost=False, return_ess=False, modif_forward=None,
+                             modif_info=None, npairs=None, seed=None, replay=None, return_idx=False):
+        return _two_filter_numpy(self, t, info, phi, loggamma, linear_cost, return_ess, modif_forward, modif_info, npairs,
+                                 seed, replay, return_idx)
+
+    two_filter_smoothing.__doc__ = _TWO_FILTER_DOC + """
+        A history kept on the host takes the NumPy route."""
 
 
 class _LazySteps:
@@ -572,6 +722,74 @@ class DeviceParticleHistory:
             max_trials = M
         max_trials = int(min(max_trials, _lib.REJECT_MAX_TRIALS))
         return self._backward(_lib.BACKWARD_REJECT, M, max_trials, seed, island, replay, return_idx)
+
+    def _two_filter_on_device(self, info, phi, loggamma):
+        from .state_space_models import QuadAddFunc, QuadLogGamma
+        smc, other = self._smc, info
+        if not isinstance(getattr(other, "hist", None), DeviceParticleHistory):
+            return False
+        if smc.qmc or other.qmc or not getattr(smc, "_fused", False) or not getattr(other, "_fused", False):
+            return False
+        if not isinstance(phi, QuadAddFunc) or not isinstance(loggamma, QuadLogGamma):
+            return False
+        model = smc.fk._device_model() if hasattr(smc.fk, "_device_model") else None
+        return model is not None and model["kind"] in _OnlineSmoother._DEVICE_KINDS and getattr(other, "_d", 1) == 1
+
+    def two_filter_smoothing(self, t, info, phi, loggamma, linear_cost=False, return_ess=False, modif_forward=None,
+                             modif_info=None, npairs=None, seed=None, replay=None, return_idx=False, island=0,
+                             island_info=0):
+        smc = self._smc
+        if t < 0 or t >= smc._n - 1:
+            raise ValueError(_TWO_FILTER_T_ERR)
+        if not self._two_filter_on_device(info, phi, loggamma):
+            self._two_filter_route = "host"
+            return _two_filter_numpy(self, t, info, phi, loggamma, linear_cost, return_ess, modif_forward, modif_info,
+                                     npairs, seed, replay, return_idx)
+        self._two_filter_route = "device"
+        ptr = lambda a, ct: a.ctypes.data_as(_lib.P(ct)) if a is not None else None
+        K = phi.K
+        est, ess = np.empty(K), _lib.c_dbl(0.0)
+        f, g3 = phi._struct(), loggamma._coef()
+        P, mf, mi, J, I = 0, None, None, None, None
+        tapes = dict.fromkeys(_TWO_FILTER_TAPES)
+        if linear_cost:
+            P = int(smc.N if npairs is None else npairs)
+            if P >= 1:
+                tapes = _two_filter_replay(replay, P)
+                if return_idx:
+                    J, I = np.empty(P, dtype=np.int64), np.empty(P, dtype=np.int64)
+            for name, a, n in (("modif_forward", modif_forward, smc.N), ("modif_info", modif_info, info.N)):
+                if a is not None:
+                    a = np.ascontiguousarray(a, dtype=np.float64)
+                    if a.shape != (n,):
+                        raise ValueError("two-filter smoothing: %s has shape %s, expected %s" % (name, a.shape, (n,)))
+                if name == "modif_forward":
+                    mf = a
+                else:
+                    mi = a
+            if seed is None and tapes["idx_fwd"] is None and (tapes["u_fwd"] is None or tapes["u_info"] is None):
+                from .core import _default_seed
+                seed = _default_seed()
+        _lib.check(_lib.lib().smc_filter_two_filter(
+            smc._f, int(island), info._f, int(island_info), int(t), _lib.TWOFILTER_ON if linear_cost else _lib.TWOFILTER_ON2,
+            ctypes.byref(f), ptr(g3, _lib.c_dbl), ptr(mf, _lib.c_dbl), ptr(mi, _lib.c_dbl), P, int(seed or 0) & (2 ** 64 - 1),
+            ptr(tapes["u_fwd"], _lib.c_dbl), ptr(tapes["u_info"], _lib.c_dbl), ptr(tapes["idx_fwd"], _lib.c_i64),
+            ptr(tapes["idx_info"], _lib.c_i64), ptr(J, _lib.c_i64), ptr(I, _lib.c_i64), ptr(est, _lib.c_dbl),
+            ctypes.byref(ess)))
+        est = est[0] if phi.scalar else est
+        if not linear_cost:
+            return est
+        out = (est, float(ess.value)) if return_ess else (est,)
+        if return_idx:
+            out = out + (J, I)
+        return out[0] if len(out) == 1 else out
+
+    two_filter_smoothing.__doc__ = _TWO_FILTER_DOC + """
+        On the device (smc_filter_two_filter) when ``info`` keeps a device-resident history too, neither filter is SQMC,
+        the forward model is one backward sampling takes, ``phi`` is a ``QuadAddFunc`` and ``loggamma`` a
+        ``QuadLogGamma``: the O(N^2) form is one all-pairs launch over the two resident histories, the O(N) form two
+        inverse-CDF draws per pair in integer CDFs.  Everything else takes the NumPy route.  ``island`` /
+        ``island_info`` pick the island of each filter (device route)."""
 
     def _backward(self, method, M, nsteps, seed, island, replay, return_idx):
         """``nsteps``: Metropolis steps (MCMC) or max_trials (rejection)."""

@@ -11,6 +11,7 @@
 #include "smc_filter_strict.h"
 #include "smc_smooth.h"
 #include "smc_online.h"
+#include "smc_twofilter.h"
 
 // ---------------------------------------------------------------------------
 // host side
@@ -2357,6 +2358,154 @@ int smc_filter_online_smooth(smc_filter* f, int island, int method, const smc_ad
     SMC_HIP_CHECK(hipMemcpyAsync(est_out_host, est, (size_t)K * 8, hipMemcpyDeviceToHost, st));
     SMC_HIP_CHECK(hipStreamSynchronize(st));
     if (nprop_out) *nprop_out = (int64_t)counts[SM_CTR_NPROPS];
+    return SMC_OK;
+}
+
+// Two-filter smoothing (smc_twofilter.h).  Reads both filters only; workspaces from the pool, launches on the context's
+// stream (the two filters share it: one stream orders the call).  One synchronisation: the download of the estimates,
+// the ESS and, when asked for, the pair indices.
+int smc_filter_two_filter(smc_filter* f, int island, smc_filter* info, int island_info, int64_t t, int method,
+                          const smc_addfunc* phi, const double* loggamma3,
+                          const double* modif_forward_host, const double* modif_info_host,
+                          int64_t npairs, uint64_t seed,
+                          const double* u_fwd_host, const double* u_info_host,
+                          const int64_t* idx_fwd_host, const int64_t* idx_info_host,
+                          int64_t* idx_fwd_out_host, int64_t* idx_info_out_host,
+                          double* est_out_host, double* ess_out_host)
+{
+    if (f) { (void)hipSetDevice(f->ctx->device); flush_rows(f); }
+    SMC_REQUIRE(f && info && phi && loggamma3 && est_out_host, "null argument");
+    SMC_REQUIRE(f->ctx == info->ctx, "the two filters must share a context");
+    flush_rows(info);
+    int rc = sm_check_filter(__func__, f, island, est_out_host);
+    if (rc != SMC_OK) return rc;
+    SMC_REQUIRE(info->kind != SMC_MODEL_MVLINGAUSS, "the information filter must be univariate");
+    SMC_REQUIRE(!info->plan.sqmc(), "SQMC information filters are not supported");
+    SMC_REQUIRE(info->a.hist == 1, "the information filter was created without a whole history (keep_history = 1)");
+    SMC_REQUIRE(island_info >= 0 && island_info < info->a.n_islands, "island_info out of range");
+    SMC_REQUIRE(method == SMC_TWOFILTER_ON2 || method == SMC_TWOFILTER_ON, "unknown method");
+    SMC_REQUIRE(phi->K >= 1 && phi->K <= OS_KMAX, "K must be 1 .. 8");
+    SMC_REQUIRE(t >= 0 && t <= f->t_host - 2, "t must be in range 0 .. T - 2, T the steps the forward filter has run");
+    const i64 ti = f->t_host - 2 - t;
+    SMC_REQUIRE(ti < info->t_host, "step T - 2 - t of the information filter has not run");
+    const bool on = method == SMC_TWOFILTER_ON;
+    const i64 Nf = f->a.N, Ni = info->a.N, P = on ? (i64)npairs : 0;
+    const bool given = on && (idx_fwd_host || idx_info_host);
+    if (on) {
+        SMC_REQUIRE(npairs >= 1 && npairs < ((int64_t)1 << 31), "npairs must be at least 1 (and below 2^31)");
+        SMC_REQUIRE(!given || (idx_fwd_host && idx_info_host), "idx_fwd and idx_info are given together");
+        for (i64 j = 0; given && j < P; ++j)
+            SMC_REQUIRE(idx_fwd_host[j] >= 0 && idx_fwd_host[j] < Nf && idx_info_host[j] >= 0 && idx_info_host[j] < Ni,
+                        "pair index out of range");
+    }
+    OsPsi psi{};
+    const int K = psi.K = phi->K;
+    memcpy(psi.c, phi->c, sizeof psi.c);
+    hipStream_t st = f->ctx->stream;
+    SmPool pool(f->ctx);
+    const double* Xf = f_X(f->a, t) + (size_t)island * Nf;
+    const double* lwf = f_lw(f->a, t) + (size_t)island * Nf;
+    const double* Xi = f_X(info->a, ti) + (size_t)island_info * Ni;
+    const double* lwg = f_lw(info->a, ti) + (size_t)island_info * Ni;
+    const unsigned nbi = (unsigned)((Ni + SMC_BLOCK - 1) / SMC_BLOCK), nbf = (unsigned)((Nf + SMC_BLOCK - 1) / SMC_BLOCK);
+    const i64 nitems = on ? P : Ni;
+    const int nchunks = (int)((nitems + TF_CHUNK - 1) / TF_CHUNK);
+    double *lwi = nullptr, *bmaxi = nullptr, *gmax = nullptr, *out = nullptr, *items = nullptr, *cmax = nullptr, *cpart = nullptr;
+    double *d_mf = nullptr, *d_mi = nullptr;
+    rc = pool.get((size_t)Ni, &lwi);
+    if (rc == SMC_OK) rc = pool.get((size_t)nbi, &bmaxi);
+    if (rc == SMC_OK) rc = pool.get((size_t)3, &gmax);
+    if (rc == SMC_OK) rc = pool.get((size_t)OS_KMAX + 1, &out);
+    if (rc == SMC_OK) rc = pool.get((size_t)nitems * (K + 2), &items);
+    if (rc == SMC_OK) rc = pool.get((size_t)nchunks, &cmax);
+    if (rc == SMC_OK) rc = pool.get((size_t)nchunks * TF_PART, &cpart);
+    if (rc == SMC_OK && on) rc = pool.upload(modif_forward_host, (size_t)Nf, &d_mf);
+    if (rc == SMC_OK && on) rc = pool.upload(modif_info_host, (size_t)Ni, &d_mi);
+    if (rc != SMC_OK) return rc;
+    const TfGamma gam{loggamma3[0], loggamma3[1], loggamma3[2], 1};
+    SMC_LAUNCH(k_tf_lwi, dim3(nbi), dim3(SMC_BLOCK), st, lwg, Xi, gam, (const double*)d_mi, Ni, lwi, bmaxi);
+    SmArgs s = sm_args(f, island, P, seed, nullptr);
+    s.t = (u32)t;
+    s.Xt = Xf; s.lwt = lwf;
+    s.aux = f->a.aux ? f->a.aux + (t + 1) : nullptr;
+    i64 *J = nullptr, *I = nullptr;
+    if (!on) {
+        const int nslices = tf_slices(Ni, Nf);
+        double *loc = nullptr, *part = nullptr;
+        rc = pool.get((size_t)Nf, &loc);
+        if (rc == SMC_OK) rc = pool.get((size_t)nslices * Ni * 4, &part);
+        if (rc != SMC_OK) return rc;
+        int slot = 1;
+        switch (f->kind) {
+        case SMC_MODEL_LINGAUSS: os_launch_loc<SMC_MODEL_LINGAUSS>(st, s, loc); slot = sm_scale_slot<SMC_MODEL_LINGAUSS>(); break;
+        case SMC_MODEL_STOCHVOL: os_launch_loc<SMC_MODEL_STOCHVOL>(st, s, loc); slot = sm_scale_slot<SMC_MODEL_STOCHVOL>(); break;
+        case SMC_MODEL_GORDON: os_launch_loc<SMC_MODEL_GORDON>(st, s, loc); slot = sm_scale_slot<SMC_MODEL_GORDON>(); break;
+        case SMC_MODEL_THETALOGISTIC:
+            os_launch_loc<SMC_MODEL_THETALOGISTIC>(st, s, loc); slot = sm_scale_slot<SMC_MODEL_THETALOGISTIC>(); break;
+        default: os_launch_loc<SMC_MODEL_DISCRETECOX>(st, s, loc); slot = sm_scale_slot<SMC_MODEL_DISCRETECOX>(); break;
+        }
+        TfOn2 o{};
+        o.Xi = Xi; o.Xf = Xf; o.lwf = lwf; o.loc = loc; o.part = part; o.p = s.p; o.slot = slot; o.Ni = Ni; o.Nf = Nf;
+        const i64 ntile = (Nf + SMC_BLOCK - 1) / SMC_BLOCK;
+        o.per_slice = ((ntile + nslices - 1) / nslices) * SMC_BLOCK;
+        const int used = (int)((Nf + o.per_slice - 1) / o.per_slice);               // (no empty slice is launched or merged)
+        SMC_LAUNCH(k_tf_on2, dim3(nbi, (unsigned)used), dim3(SMC_BLOCK), st, o);
+        SMC_LAUNCH(k_tf_merge, dim3(nbi), dim3(SMC_BLOCK), st, psi, Xi, (const double*)lwi, (const double*)part, used, Ni, items);
+    } else {
+        TfPairs q{};
+        i64 *J_in = nullptr, *I_in = nullptr;
+        double *d_uf = nullptr, *d_ui = nullptr;
+        rc = pool.get((size_t)P, &J);
+        if (rc == SMC_OK) rc = pool.get((size_t)P, &I);
+        if (rc == SMC_OK && given) rc = pool.upload((const i64*)idx_fwd_host, (size_t)P, &J_in);
+        if (rc == SMC_OK && given) rc = pool.upload((const i64*)idx_info_host, (size_t)P, &I_in);
+        if (rc == SMC_OK && !given) rc = pool.upload(u_fwd_host, (size_t)P, &d_uf);
+        if (rc == SMC_OK && !given) rc = pool.upload(u_info_host, (size_t)P, &d_ui);
+        if (rc != SMC_OK) return rc;
+        if (!given) {
+            const i64 Nmax = Nf > Ni ? Nf : Ni;
+            u64 *cdf_f = nullptr, *cdf_i = nullptr, *tot = nullptr;
+            rc = pool.get((size_t)Nf, &cdf_f);
+            if (rc == SMC_OK) rc = pool.get((size_t)Ni, &cdf_i);
+            if (rc == SMC_OK) rc = pool.get((size_t)((Nmax + SM_CHUNK - 1) / SM_CHUNK), &tot);
+            if (rc != SMC_OK) return rc;
+            if (d_mf) {
+                double *lf = nullptr, *bmaxf = nullptr;
+                rc = pool.get((size_t)Nf, &lf);
+                if (rc == SMC_OK) rc = pool.get((size_t)nbf, &bmaxf);
+                if (rc != SMC_OK) return rc;
+                const TfGamma none{0.0, 0.0, 0.0, 0};
+                SMC_LAUNCH(k_tf_lwi, dim3(nbf), dim3(SMC_BLOCK), st, lwf, Xf, none, (const double*)d_mf, Nf, lf, bmaxf);
+                tf_cdf_of(st, lf, bmaxf, Nf, gmax + 1, tot, cdf_f);
+            } else {
+                sm_weights_cdf(f, island, t, s, tot, cdf_f);
+            }
+            tf_cdf_of(st, lwi, bmaxi, Ni, gmax + 2, tot, cdf_i);                     // (the stream orders the two uses of tot)
+            q.cdf_f = cdf_f; q.cdf_i = cdf_i;
+        }
+        q.Xi = Xi; q.u_f = d_uf; q.u_i = d_ui; q.J_in = J_in; q.I_in = I_in; q.mf = d_mf; q.mi = d_mi;
+        q.J = J; q.I = I; q.items = items; q.Ni = Ni; q.P = P;
+        switch (f->kind) {
+        case SMC_MODEL_LINGAUSS: tf_launch_pairs<SMC_MODEL_LINGAUSS>(st, s, q, psi); break;
+        case SMC_MODEL_STOCHVOL: tf_launch_pairs<SMC_MODEL_STOCHVOL>(st, s, q, psi); break;
+        case SMC_MODEL_GORDON: tf_launch_pairs<SMC_MODEL_GORDON>(st, s, q, psi); break;
+        case SMC_MODEL_THETALOGISTIC: tf_launch_pairs<SMC_MODEL_THETALOGISTIC>(st, s, q, psi); break;
+        default: tf_launch_pairs<SMC_MODEL_DISCRETECOX>(st, s, q, psi); break;
+        }
+    }
+    SMC_LAUNCH(k_tf_item_max, dim3((unsigned)nchunks), dim3(SMC_BLOCK), st, (const double*)items, K + 2, nitems, cmax);
+    SMC_LAUNCH(k_tf_max_final, dim3(1), dim3(SMC_BLOCK), st, (const double*)cmax, (i64)nchunks, gmax);
+    SMC_LAUNCH(k_tf_item_sums, dim3((unsigned)nchunks), dim3(SMC_BLOCK), st, (const double*)items, K + 2, nitems, K,
+               (const double*)gmax, cpart);
+    SMC_LAUNCH(k_tf_final, dim3(1), dim3(64), st, (const double*)cpart, nchunks, K, out);
+    SMC_LAUNCH_CHECK();
+    double res[OS_KMAX + 1];
+    SMC_HIP_CHECK(hipMemcpyAsync(res, out, sizeof res, hipMemcpyDeviceToHost, st));
+    if (on && idx_fwd_out_host) SMC_HIP_CHECK(hipMemcpyAsync(idx_fwd_out_host, J, (size_t)P * 8, hipMemcpyDeviceToHost, st));
+    if (on && idx_info_out_host) SMC_HIP_CHECK(hipMemcpyAsync(idx_info_out_host, I, (size_t)P * 8, hipMemcpyDeviceToHost, st));
+    SMC_HIP_CHECK(hipStreamSynchronize(st));
+    for (int k = 0; k < K; ++k) est_out_host[k] = res[k];
+    if (ess_out_host) *ess_out_host = res[OS_KMAX];
     return SMC_OK;
 }
 

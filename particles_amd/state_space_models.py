@@ -70,6 +70,22 @@ class QuadAddFunc:
         return f
 
 
+class QuadLogGamma:
+    """``loggamma`` of two-filter smoothing in closed form, ``loggamma(x) = g0 + g1 x + g2 x**2`` -- the log-density of
+    any Gaussian pseudo-prior of the information filter, up to its constant -- so that
+    ``DeviceParticleHistory.two_filter_smoothing`` can evaluate it on the device."""
+
+    def __init__(self, g0, g1, g2):
+        self.g0, self.g1, self.g2 = float(g0), float(g1), float(g2)
+
+    def __call__(self, x):
+        x = np.asarray(x, dtype=np.float64)
+        return self.g0 + self.g1 * x + self.g2 * x ** 2
+
+    def _coef(self):
+        return np.array([self.g0, self.g1, self.g2], dtype=np.float64)
+
+
 class StateSpaceModel:
     """Base class for state-space models (state_space_models.py:172-296): parameters are
     attributes (class-level ``default_params`` overridden by keyword arguments), the model is

@@ -398,6 +398,17 @@ int smc_filter_reseed(smc_filter* f, uint64_t seed);
  * with K = 1 (systematic: rand(1)), N (stratified: rand(N)) or N (multinomial:
  * the SORTED uniforms).  Slots of steps that do not resample are ignored. */
 int smc_filter_set_replay(smc_filter* f, const double* z, const double* u);
+/* Conditional SMC (mcmc.py:453-475, the state update of Particle Gibbs), before the first step: particle 0 of island i
+ * follows xstar_dev[i, :] -- a DEVICE buffer (n_islands, T) the caller owns, like the replay tapes -- and A[0] = 0 on
+ * every resampling step; smc_filter_step then runs the one-launch conditional filter (k_csmc_small).
+ * The N - 1 free ancestors of a resampling step are iid draws from W_{t-1}, each the inverse of one uniform in the integer
+ * CDF of backward sampling: the multinomial replay tape's slots 1 .. N-1 (slot 0 is ignored), or Philox stream 6, key
+ * opts.seed, counter (n, t, island, 6), word x01 -> [0, 1).  The move draws the normals of the unconditional filter.
+ * smc_filter_clone shares the pointer; a saved state does not carry it (set it again on the re-created filter).
+ * SMC_ERR_INVALID: anything but a bootstrap filter of LINGAUSS / STOCHVOL / GORDON / THETALOGISTIC / DISCRETECOX, N > 1024,
+ * a scheme other than multinomial, keep_history != 1, moments, SMC_FLAG_STRICT_ANCESTORS, SMC_FLAG_SQMC, use_graph, a
+ * theta level or profiling (smc_filter_profile is refused afterwards).  SMC_ERR_STATE: the filter has stepped. */
+int smc_filter_set_conditional(smc_filter* f, const double* xstar_dev);
 /* Enqueue `nsteps` time steps (asynchronous).  Steps beyond T are no-ops. */
 int smc_filter_step(smc_filter* f, int64_t nsteps);
 int smc_filter_sync(smc_filter* f);
@@ -506,6 +517,16 @@ int smc_filter_backward_sample(smc_filter* f, int island, int method, int64_t M,
                                const int64_t* idx_last_host, const double* u_last_host,
                                const double* u_host, const double* u_acc_host,
                                int64_t* idx_out_host, double* paths_out_host);
+/* The same kinds, N <= 1024, keep_history == 1, conditional or not: ONE new trajectory per island over the t steps run, all
+ * islands in one launch (k_csmc_path).  backward = 0: the genealogical line of a particle drawn from the last weights
+ * (extract_one_trajectory); backward = 1: exact backward sampling -- for island i the indices
+ * smc_filter_backward_sample(f, i, SMC_BACKWARD_ON2, 1, ...) returns from the same uniforms.  u_last_host (n_islands) /
+ * u_host (t-1, n_islands; backward only): replay tapes or NULL (Philox stream 3, key `seed`, counter (0, s, island, 3)).
+ * Outputs, each or NULL (one at least): idx_out_host (n_islands, t) int64, paths_out_host (n_islands, t) fp64,
+ * paths_out_dev the same on the DEVICE -- with t = T what the next smc_filter_set_conditional takes.  Reads the history
+ * only.  SMC_ERR_INVALID: another kind, SQMC, N > 1024, keep_history != 1, no step executed, no output. */
+int smc_filter_csmc_paths(smc_filter* f, int backward, uint64_t seed, const double* u_last_host, const double* u_host,
+                          int64_t* idx_out_host, double* paths_out_host, double* paths_out_dev);
 /* The same filters: M trajectories by the hybrid of rejection and exact backward sampling (backward_sampling_reject,
  * smoothing.py:352-423; Dau & Chopin 2022).  Per step s = t-2 .. 0 and trajectory m, trial i = 0 .. max_trials-1 proposes
  * prop_i from W_s and accepts iff log(u_acc[i]) < log p_{s+1}(x_{s+1} | X_s[prop_i]) - log_bound_host[s]; idx[s, m] is the

@@ -140,6 +140,8 @@ SIGNATURES = {
     "smc_comm_allgather_f64_async": (c_int, [c_vp, c_vp, c_i64, c_vp]),
     "smc_comm_rank": (c_int, [c_vp, P(c_int), P(c_int)]),
     "smc_filter_set_replay": (c_int, [c_vp, c_vp, c_vp]),
+    "smc_filter_set_conditional": (c_int, [c_vp, c_vp]),
+    "smc_filter_csmc_paths": (c_int, [c_vp, c_int, c_u64, P(c_dbl), P(c_dbl), P(c_i64), P(c_dbl), c_vp]),
     "smc_filter_step": (c_int, [c_vp, c_i64]),
     "smc_filter_sync": (c_int, [c_vp]),
     "smc_filter_t": (c_int, [c_vp, P(c_i64)]),

@@ -9,7 +9,8 @@ module plugs into exactly those:
     pmmh = particles.mcmc.PMMH(..., smc_cls=hip.HipSMC())          # fused device filter per theta
     alg = hip.HipSMC()(fk=particles.smc_samplers.SMC2(..., wastefree=False), N=...)   # SMC^2 on the device class
     hip.register_into(particles.resampling)                         # 'systematic_hip', ...
-    hip.install()      # particles.SMC -> HipSMC, for callers that name particles.SMC themselves
+    hip.install()      # particles.SMC -> HipSMC, for callers that name particles.SMC themselves; and
+                       # particles.mcmc.CSMC -> HipCSMC: ParticleGibbs then runs both of its filters on the device
 
 ``adapt(fk)`` maps a reference Feynman-Kac object -- ``Bootstrap`` / ``GuidedPF`` (/ APF) of a STOCK
 state-space model, recognised by exact class, parameters read from its ``__dict__`` -- onto the
@@ -304,6 +305,31 @@ def HipSMC():
     return _HIP_SMC
 
 
+_HIP_CSMC = None
+
+
+def HipCSMC():
+    """``class HipCSMC(particles.mcmc.CSMC)`` whose constructor returns a ``particles_amd.mcmc.CSMC`` -- the conditional
+    filter on the device -- when ``adapt(fk)`` succeeds and the device runs that configuration conditional (Bootstrap of
+    LinearGauss, StochVol, Gordon_etal, ThetaLogistic, DiscreteCox; N <= 1024), and the reference's ``CSMC`` otherwise."""
+    global _HIP_CSMC
+    if _HIP_CSMC is None:
+        from particles import mcmc as rmcmc
+        from . import mcmc as dmcmc
+
+        base = getattr(rmcmc, "_csmc_before_hip", rmcmc.CSMC)
+
+        class HipCSMC(base):
+            def __new__(cls, fk=None, N=100, ESSrmin=0.5, xstar=None, **kw):
+                mine = adapt(fk) if fk is not None else None
+                if mine is None or not dmcmc.device_conditional(mine, N):
+                    return super().__new__(cls)            # the reference's own path
+                return dmcmc.CSMC(fk=mine, N=N, ESSrmin=ESSrmin, xstar=xstar, **kw)     # not an instance of cls
+
+        _HIP_CSMC = HipCSMC
+    return _HIP_CSMC
+
+
 class _HipRun:
     """The worker functor of the reference's multiSMC (core.py:415-423 ``_picklable_f``) with HipSMC where it names
     ``SMC``: picklable, so the reference's loky workers (utils.py:178-186) can receive it -- each worker process then
@@ -335,6 +361,13 @@ def install():
     if not hasattr(particles, "_smc_before_hip"):
         particles._smc_before_hip = particles.SMC
     particles.SMC = HipSMC()
+    try:        # Particle Gibbs (mcmc.py:606-619) names its conditional filter as the module's CSMC
+        from particles import mcmc as rmcmc
+    except ImportError:
+        return
+    if not hasattr(rmcmc, "_csmc_before_hip"):
+        rmcmc._csmc_before_hip = rmcmc.CSMC
+    rmcmc.CSMC = HipCSMC()
 
 
 def uninstall():
@@ -342,6 +375,13 @@ def uninstall():
     if hasattr(particles, "_smc_before_hip"):
         particles.SMC = particles._smc_before_hip
         del particles._smc_before_hip
+    try:
+        from particles import mcmc as rmcmc
+    except ImportError:
+        return
+    if hasattr(rmcmc, "_csmc_before_hip"):
+        rmcmc.CSMC = rmcmc._csmc_before_hip
+        del rmcmc._csmc_before_hip
 
 
 def register_into(rs_module, suffix="_hip", override=False):

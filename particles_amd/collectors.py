@@ -684,7 +684,34 @@ class DeviceParticleHistory:
         replay : dict of uniforms to use instead: ``idx_last`` (M,) int64 or ``u_last`` (M,) for the
             last row, ``u`` (T-1, M) for the backward steps.
         """
+        if int(M) == 1 and getattr(self._smc, "_cond_device", False):
+            out = self._one_launch(seed, island, replay, return_idx)
+            if out is not None:
+                return out
         return self._backward(_lib.BACKWARD_ON2, M, 1, seed, island, replay, return_idx)
+
+    def _one_launch(self, seed, island, replay, return_idx):
+        """``backward_sampling_ON2(1)`` on a conditional filter (``mcmc.CSMC``): the launch that walks every island's
+        history at once (smc_filter_csmc_paths) -- the same indices from the same uniforms.  None: arguments the
+        general route takes (or refuses)."""
+        smc = self._smc
+        C, T = smc.n_islands, smc._n
+        replay = dict(replay or {})
+        if T < 1 or not 0 <= int(island) < C or set(replay) - {"u_last", "u"}:
+            return None
+        tapes = {}
+        for k, shp in (("u_last", (1,)), ("u", (T - 1, 1))):
+            if replay.get(k) is None:
+                continue
+            a = np.asarray(replay[k], dtype=np.float64)
+            if a.shape != shp:
+                return None
+            tapes[k] = np.full(shp[:-1] + (C,), 0.5)          # (the other islands' draws are not handed out)
+            tapes[k][..., int(island)] = a[..., 0]
+        from .mcmc import new_paths
+        paths, idx = new_paths(smc, True, seed, tapes, True)
+        out = [paths[int(island), t] for t in range(T)]
+        return (out, idx[int(island)].reshape(T, 1).copy()) if return_idx else out
 
     def backward_sampling_mcmc(self, M, nsteps=1, seed=None, island=0, replay=None, return_idx=False):
         """MCMC backward sampling (smoothing.py:313-350; Dau & Chopin 2022), on the device: each

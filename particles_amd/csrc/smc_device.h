@@ -25,6 +25,7 @@
 #define SMC_STREAM_BACKWARD 3u    /* backward sampling (smc_smooth.h): counter (i M + m, t, island, 3) */
 #define SMC_STREAM_REJECT 4u      /* rejection trials (smc_smooth.h): counter (m, t, island, 4 | i << 8), i < 2^24 */
 #define SMC_STREAM_TWOFILTER 5u   /* two-filter smoothing pairs (smc_twofilter.h): counter (j, t, island, 5) */
+#define SMC_STREAM_CSMC 6u        /* ancestors of the conditional filter (smc_csmc.h): counter (n, t, island, 6) */
 
 __device__ __forceinline__ int smc_lane() { return (int)(threadIdx.x & 63u); }
 __device__ __forceinline__ int smc_wave() { return (int)(threadIdx.x >> 6); }

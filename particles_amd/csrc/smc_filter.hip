@@ -12,6 +12,7 @@
 #include "smc_smooth.h"
 #include "smc_online.h"
 #include "smc_twofilter.h"
+#include "smc_csmc.h"
 
 // ---------------------------------------------------------------------------
 // host side
@@ -144,6 +145,9 @@ struct smc_filter {
     smc_comm* th_comm = nullptr;
     int th_n = 0;
     double *th_send = nullptr, *th_recv = nullptr;
+    // conditional SMC (smc_filter_set_conditional, smc_csmc.h): the retained trajectories (n_islands, T), caller-owned
+    // like the replay tapes; smc_filter_step then runs k_csmc_small.  Not part of a saved state; shared by a clone.
+    const double* xstar = nullptr;
 };
 
 // the uniforms of a multinomial step are drawn on the device (no replay tape: smc_filter_set_replay may set one later)
@@ -1212,6 +1216,57 @@ static void launch_small(smc_filter* f, int nsteps)
 #undef S_CASE
 }
 
+// Conditional SMC (smc_csmc.h): particle 0 of every island follows xstar (n_islands, T), a device buffer the caller owns.
+// Accepted where k_csmc_small can run -- a fresh bootstrap filter of a kind backward sampling takes, one tile,
+// multinomial, whole history, none of the side kernels; smc_filter_step then launches k_csmc_small (Philox or replay).
+static bool csmc_kind_ok(int kind)
+{
+    return kind == SMC_MODEL_LINGAUSS || kind == SMC_MODEL_STOCHVOL || kind == SMC_MODEL_GORDON ||
+           kind == SMC_MODEL_THETALOGISTIC || kind == SMC_MODEL_DISCRETECOX;
+}
+int smc_filter_set_conditional(smc_filter* f, const double* xstar_dev)
+{
+    SMC_REQUIRE(f && xstar_dev, "null argument");
+    SMC_REQUIRE(csmc_kind_ok(f->kind) && f->fk == SMC_FK_BOOTSTRAP,
+                "conditional SMC on the device: bootstrap filters of LINGAUSS, STOCHVOL, GORDON, THETALOGISTIC, DISCRETECOX");
+    SMC_REQUIRE(!f->plan.sqmc(), "conditional SMC on the device: not with SMC_FLAG_SQMC");
+    SMC_REQUIRE(!f->plan.strict(), "conditional SMC on the device: not with SMC_FLAG_STRICT_ANCESTORS");
+    SMC_REQUIRE(!f->use_graph, "conditional SMC on the device: not with use_graph");
+    SMC_REQUIRE(f->a.N <= F_TILE, "conditional SMC on the device: N <= 1024 (one workgroup per filter)");
+    SMC_REQUIRE(f->a.scheme == SMC_MULTINOMIAL, "conditional SMC on the device: multinomial resampling only");
+    SMC_REQUIRE(f->a.hist == 1, "conditional SMC on the device: the filter must keep its whole history (keep_history = 1)");
+    SMC_REQUIRE(!f->a.mom, "conditional SMC on the device: no device moments");
+    SMC_REQUIRE(f->plan.small && !f->lwth && !f->prof,
+                "conditional SMC on the device: the one-launch filter must be available (no SMC_PATH_NO_SMALL, theta level "
+                "or profiling)");
+    if (f->t_host != 0) {
+        smc_set_error("smc_filter_set_conditional: the retained trajectory must be set before the first step");
+        return SMC_ERR_STATE;
+    }
+    f->xstar = xstar_dev;
+    return SMC_OK;
+}
+
+static void launch_csmc(smc_filter* f, int nsteps)
+{
+    hipStream_t st = f->ctx->stream;
+    const dim3 grid(1, f->a.n_islands);
+    f->a.par = -1;
+#define C_CASE(KINDV)                                                                                         \
+    case KINDV:                                                                                               \
+        if (f->a.N <= 256) SMC_LAUNCH((k_csmc_small<KINDV, 64>), grid, dim3(64), st, f->a, nsteps, f->xstar); \
+        else SMC_LAUNCH((k_csmc_small<KINDV, SMC_BLOCK>), grid, dim3(SMC_BLOCK), st, f->a, nsteps, f->xstar); \
+        break;
+    switch (f->kind) {
+        C_CASE(SMC_MODEL_LINGAUSS)
+        C_CASE(SMC_MODEL_STOCHVOL)
+        C_CASE(SMC_MODEL_GORDON)
+        C_CASE(SMC_MODEL_THETALOGISTIC)
+        C_CASE(SMC_MODEL_DISCRETECOX)
+    }
+#undef C_CASE
+}
+
 // The summary row of step t (ESS, evidence terms, the (K, 1/s) its weights are normalised with) is written by the
 // reduction that OPENS step t + 1; behind the last step enqueued nobody has done it yet.  k_flush2 does -- when
 // somebody asks for results (every accessor below calls this), not at the end of every smc_filter_step call: a
@@ -1238,6 +1293,16 @@ int smc_filter_step(smc_filter* f, int64_t nsteps)
         smc_set_error("the auxiliary particle filter with N <= 1024 runs on the one-launch filter only (no "
                       "profiling, no Philox multinomial)");
         return SMC_ERR_STATE;
+    }
+    if (todo > 0 && f->xstar) {
+        if (f->lwth || f->prof) {
+            smc_set_error("a conditional filter runs neither under a theta level nor with profiling on");
+            return SMC_ERR_STATE;
+        }
+        launch_csmc(f, (int)(todo > 0x7fffffff ? 0x7fffffff : todo));
+        SMC_LAUNCH_CHECK();
+        f->t_host += todo;
+        return SMC_OK;
     }
     if (todo > 0 && f->lwth) {
         // theta level on: the theta-weights are updated behind every step (and may freeze the batch)
@@ -2139,6 +2204,56 @@ int smc_filter_backward_sample(smc_filter* f, int island, int method, int64_t M,
     return sm_download(f, island, M, idx, paths, idx_out_host, paths_out_host);
 }
 
+// One new trajectory per island in ONE launch (smc_csmc.h, k_csmc_path): the state update of Particle Gibbs for all chains.
+// backward = 0: the genealogy of a particle drawn from the last weights; 1: backward sampling, for every island the
+// indices smc_filter_backward_sample(SMC_BACKWARD_ON2, M = 1) returns from the same uniforms.
+int smc_filter_csmc_paths(smc_filter* f, int backward, uint64_t seed, const double* u_last_host, const double* u_host,
+                          int64_t* idx_out_host, double* paths_out_host, double* paths_out_dev)
+{
+    if (f) { (void)hipSetDevice(f->ctx->device); flush_rows(f); }
+    SMC_REQUIRE(f && (idx_out_host || paths_out_host || paths_out_dev), "null filter, or no output asked for");
+    SMC_REQUIRE(!f->plan.sqmc(), "SQMC filters are not supported");
+    SMC_REQUIRE(csmc_kind_ok(f->kind), "model kind is not supported: LINGAUSS, STOCHVOL, GORDON, THETALOGISTIC, DISCRETECOX");
+    SMC_REQUIRE(f->a.hist == 1, "the filter was created without a whole history (keep_history = 1)");
+    SMC_REQUIRE(f->a.N <= F_TILE, "N <= 1024: one workgroup walks an island's history");
+    SMC_REQUIRE(f->t_host >= 1, "no step has run yet");
+    const i64 t = f->t_host;
+    const size_t C = (size_t)f->a.n_islands;
+    hipStream_t st = f->ctx->stream;
+    SmPool pool(f->ctx);
+    i64* idx = nullptr;
+    double *paths = paths_out_dev, *d_ulast = nullptr, *d_u = nullptr;
+    int rc = pool.get(C * t, &idx);
+    if (rc == SMC_OK && !paths) rc = pool.get(C * t, &paths);
+    if (rc == SMC_OK) rc = pool.upload(u_last_host, C, &d_ulast);
+    if (rc == SMC_OK && backward) rc = pool.upload(u_host, (size_t)(t - 1) * C, &d_u);
+    if (rc != SMC_OK) return rc;
+    const dim3 grid(1, f->a.n_islands);
+    const int kform = f->plan.two_level ? 1 : 0, bw = backward ? 1 : 0;
+#define CP_CASE(KINDV)                                                                                                   \
+    case KINDV:                                                                                                          \
+        if (f->a.N <= 256)                                                                                               \
+            SMC_LAUNCH((k_csmc_path<KINDV, 64>), grid, dim3(64), st, f->a, t, bw, kform, (u64)seed, (const double*)d_ulast, \
+                       (const double*)d_u, idx, paths);                                                                  \
+        else                                                                                                             \
+            SMC_LAUNCH((k_csmc_path<KINDV, SMC_BLOCK>), grid, dim3(SMC_BLOCK), st, f->a, t, bw, kform, (u64)seed,        \
+                       (const double*)d_ulast, (const double*)d_u, idx, paths);                                          \
+        break;
+    switch (f->kind) {
+        CP_CASE(SMC_MODEL_LINGAUSS)
+        CP_CASE(SMC_MODEL_STOCHVOL)
+        CP_CASE(SMC_MODEL_GORDON)
+        CP_CASE(SMC_MODEL_THETALOGISTIC)
+        CP_CASE(SMC_MODEL_DISCRETECOX)
+    }
+#undef CP_CASE
+    SMC_LAUNCH_CHECK();
+    if (idx_out_host) SMC_HIP_CHECK(hipMemcpyAsync(idx_out_host, idx, C * t * 8, hipMemcpyDeviceToHost, st));
+    if (paths_out_host) SMC_HIP_CHECK(hipMemcpyAsync(paths_out_host, paths, C * t * 8, hipMemcpyDeviceToHost, st));
+    SMC_HIP_CHECK(hipStreamSynchronize(st));
+    return SMC_OK;
+}
+
 // The hybrid of rejection trials and the exact draw (smc_smooth.h, k_sm_reject_*).  Per backward step: the CDF of W_b,
 // then three launches whose grids the host sizes by M -- the lists' counts are read on the device, so the loop has no
 // synchronisation.  The counters of all steps are zeroed once, in front of the loop.
@@ -2520,6 +2635,7 @@ int smc_filter_info(smc_filter* f, double* bytes_per_particle_step, int* kernels
 int smc_filter_profile(smc_filter* f, int enable)
 {
     SMC_REQUIRE(f, "null filter");
+    SMC_REQUIRE(!(enable && f->xstar), "a conditional filter (smc_filter_set_conditional) cannot be profiled per step");
     f->prof = enable != 0;
     f->prof_n = 0;
     if (f->prof && f->ev.empty()) {
@@ -2556,7 +2672,8 @@ int smc_filter_describe(smc_filter* f, char* out, size_t n)
     // (the strict kinds do not list their spacings and moments launches, SQMC on the flat step not its moments: kept as
     //  they are, tests and the benchmark's model compare these strings)
     std::string s;
-    if (small_filter_ok(f)) s = "k_filter_small";
+    if (f->xstar) s = "k_csmc_small";
+    else if (small_filter_ok(f)) s = "k_filter_small";
     else if (p.sq_flat)
         s = std::string(mv ? "smc_hilbert_sort" : "k_rs_sort") + "+k_sobol+k_sqmv_tapes+" + ancestors + "+k_sqmv_compose+" +
             (mv ? "k_propagate_mv" + mv_chunks : std::string("k_propagate"));

@@ -852,6 +852,28 @@ static int fill_filter(smc_filter* f, const SlabLayout& L, const smc_model* mode
     return SMC_OK;
 }
 
+// The univariate kinds SmTrans evaluates the transition density of -- what backward sampling, on-line and two-filter
+// smoothing and conditional SMC take -- are named here and nowhere else: fn(std::integral_constant<int, kind>{}) is the one
+// switch from a kind to a template argument of their launches.  No default: another kind launches nothing, and every caller
+// has passed sm_kind_ok.  The lambdas hold launches only (SMC_REQUIRE, SMC_HIP_CHECK return from the function they stand in).
+template <class F>
+static void sm_with_kind(int kind, F&& fn)
+{
+    switch (kind) {
+    case SMC_MODEL_LINGAUSS: fn(std::integral_constant<int, SMC_MODEL_LINGAUSS>{}); break;
+    case SMC_MODEL_STOCHVOL: fn(std::integral_constant<int, SMC_MODEL_STOCHVOL>{}); break;
+    case SMC_MODEL_GORDON: fn(std::integral_constant<int, SMC_MODEL_GORDON>{}); break;
+    case SMC_MODEL_THETALOGISTIC: fn(std::integral_constant<int, SMC_MODEL_THETALOGISTIC>{}); break;
+    case SMC_MODEL_DISCRETECOX: fn(std::integral_constant<int, SMC_MODEL_DISCRETECOX>{}); break;
+    }
+}
+static bool sm_kind_ok(int kind)
+{
+    bool ok = false;
+    sm_with_kind(kind, [&](auto) { ok = true; });
+    return ok;
+}
+
 extern "C" {
 
 static int filter_fetch(smc_filter* f, int field, i64 s, int island, void* out_host);
@@ -1219,15 +1241,10 @@ static void launch_small(smc_filter* f, int nsteps)
 // Conditional SMC (smc_csmc.h): particle 0 of every island follows xstar (n_islands, T), a device buffer the caller owns.
 // Accepted where k_csmc_small can run -- a fresh bootstrap filter of a kind backward sampling takes, one tile,
 // multinomial, whole history, none of the side kernels; smc_filter_step then launches k_csmc_small (Philox or replay).
-static bool csmc_kind_ok(int kind)
-{
-    return kind == SMC_MODEL_LINGAUSS || kind == SMC_MODEL_STOCHVOL || kind == SMC_MODEL_GORDON ||
-           kind == SMC_MODEL_THETALOGISTIC || kind == SMC_MODEL_DISCRETECOX;
-}
 int smc_filter_set_conditional(smc_filter* f, const double* xstar_dev)
 {
     SMC_REQUIRE(f && xstar_dev, "null argument");
-    SMC_REQUIRE(csmc_kind_ok(f->kind) && f->fk == SMC_FK_BOOTSTRAP,
+    SMC_REQUIRE(sm_kind_ok(f->kind) && f->fk == SMC_FK_BOOTSTRAP,
                 "conditional SMC on the device: bootstrap filters of LINGAUSS, STOCHVOL, GORDON, THETALOGISTIC, DISCRETECOX");
     SMC_REQUIRE(!f->plan.sqmc(), "conditional SMC on the device: not with SMC_FLAG_SQMC");
     SMC_REQUIRE(!f->plan.strict(), "conditional SMC on the device: not with SMC_FLAG_STRICT_ANCESTORS");
@@ -1252,19 +1269,11 @@ static void launch_csmc(smc_filter* f, int nsteps)
     hipStream_t st = f->ctx->stream;
     const dim3 grid(1, f->a.n_islands);
     f->a.par = -1;
-#define C_CASE(KINDV)                                                                                         \
-    case KINDV:                                                                                               \
-        if (f->a.N <= 256) SMC_LAUNCH((k_csmc_small<KINDV, 64>), grid, dim3(64), st, f->a, nsteps, f->xstar); \
-        else SMC_LAUNCH((k_csmc_small<KINDV, SMC_BLOCK>), grid, dim3(SMC_BLOCK), st, f->a, nsteps, f->xstar); \
-        break;
-    switch (f->kind) {
-        C_CASE(SMC_MODEL_LINGAUSS)
-        C_CASE(SMC_MODEL_STOCHVOL)
-        C_CASE(SMC_MODEL_GORDON)
-        C_CASE(SMC_MODEL_THETALOGISTIC)
-        C_CASE(SMC_MODEL_DISCRETECOX)
-    }
-#undef C_CASE
+    sm_with_kind(f->kind, [&](auto k) {
+        constexpr int KIND = decltype(k)::value;
+        if (f->a.N <= 256) SMC_LAUNCH((k_csmc_small<KIND, 64>), grid, dim3(64), st, f->a, nsteps, f->xstar);
+        else SMC_LAUNCH((k_csmc_small<KIND, SMC_BLOCK>), grid, dim3(SMC_BLOCK), st, f->a, nsteps, f->xstar);
+    });
 }
 
 // The summary row of step t (ESS, evidence terms, the (K, 1/s) its weights are normalised with) is written by the
@@ -2032,42 +2041,24 @@ int smc_filter_one_trajectory(smc_filter* f, int island, int64_t n_last, double*
 }
 
 // Backward sampling over the resident history (smc_smooth.h).  Workspaces come from the context's pool and are used
-// on its stream only; the one synchronisation is the download at the end.  The sm_* helpers serve both entries
-// (`who` names the entry in the message, as SMC_REQUIRE does).
-#define SM_REQUIRE(who, cond, msg)                             \
-    do {                                                       \
-        if (!(cond)) {                                         \
-            smc_set_error("%s: %s", who, msg);                 \
-            return SMC_ERR_INVALID;                            \
-        }                                                      \
-    } while (0)
-static int sm_check_filter(const char* who, smc_filter* f, int island, const void* idx_out_host, bool whole_history = true)
+// on its stream only; the one synchronisation is the download at the end.  The sm_* helpers serve all the smoothing
+// entries; a check hands back the text of the first refusal (null: none) and the entry raises it with SMC_REQUIRE.
+static const char* sm_check_filter(smc_filter* f, int island, const void* idx_out_host, bool whole_history = true)
 {
-    SM_REQUIRE(who, f && idx_out_host, "null argument");
-    SM_REQUIRE(who, !f->plan.sqmc(), "SQMC filters are not supported (backward_sampling_qmc is a different algorithm)");
-    SM_REQUIRE(who, f->kind != SMC_MODEL_SVLEVERAGE, "model kind SVLEVERAGE is not supported: its transition reads y_{t-1}");
-    SM_REQUIRE(who, f->kind != SMC_MODEL_MVLINGAUSS, "model kind MVLINGAUSS is not supported: univariate models only");
-    SM_REQUIRE(who, f->kind == SMC_MODEL_LINGAUSS || f->kind == SMC_MODEL_STOCHVOL || f->kind == SMC_MODEL_GORDON ||
-               f->kind == SMC_MODEL_THETALOGISTIC || f->kind == SMC_MODEL_DISCRETECOX, "model kind is not supported");
-    SM_REQUIRE(who, !whole_history || f->a.hist == 1, "the filter was created without a whole history (keep_history = 1)");
-    SM_REQUIRE(who, island >= 0 && island < f->a.n_islands, "island out of range");
-    return SMC_OK;
+    if (!(f && idx_out_host)) return "null argument";
+    if (!(!f->plan.sqmc())) return "SQMC filters are not supported (backward_sampling_qmc is a different algorithm)";
+    if (!(f->kind != SMC_MODEL_SVLEVERAGE)) return "model kind SVLEVERAGE is not supported: its transition reads y_{t-1}";
+    if (!(f->kind != SMC_MODEL_MVLINGAUSS)) return "model kind MVLINGAUSS is not supported: univariate models only";
+    if (!sm_kind_ok(f->kind)) return "model kind is not supported";
+    if (!(!whole_history || f->a.hist == 1)) return "the filter was created without a whole history (keep_history = 1)";
+    if (!(island >= 0 && island < f->a.n_islands)) return "island out of range";
+    return nullptr;
 }
-static int sm_check_trajectories(const char* who, smc_filter* f, int64_t M)
+static const char* sm_check_idx_last(smc_filter* f, int64_t M, const int64_t* idx_last_host)
 {
-    SM_REQUIRE(who, M >= 1 && M < ((int64_t)1 << 31), "M must be at least 1 (and below 2^31)");
-    return SMC_OK;
-}
-static int sm_check_steps(const char* who, smc_filter* f)
-{
-    SM_REQUIRE(who, f->t_host >= 1, "no step has run yet");
-    return SMC_OK;
-}
-static int sm_check_idx_last(const char* who, smc_filter* f, int64_t M, const int64_t* idx_last_host)
-{
-    if (idx_last_host)
-        for (i64 m = 0; m < M; ++m) SM_REQUIRE(who, idx_last_host[m] >= 0 && idx_last_host[m] < f->a.N, "idx_last out of range");
-    return SMC_OK;
+    for (i64 m = 0; idx_last_host && m < M; ++m)
+        if (!(idx_last_host[m] >= 0 && idx_last_host[m] < f->a.N)) return "idx_last out of range";
+    return nullptr;
 }
 // what every launch of one call shares
 static SmArgs sm_args(smc_filter* f, int island, int64_t M, uint64_t seed, const u64* cdf)
@@ -2083,10 +2074,14 @@ static SmArgs sm_args(smc_filter* f, int island, int64_t M, uint64_t seed, const
     s.cdf = cdf;
     return s;
 }
-static const double* sm_rows(smc_filter* f, int island)
-{
-    return f->a.summ + (size_t)island * (f->a.T + 1) * SUMM_STRIDE;
-}
+// every entry opens with this: the filter's device, and the summary row behind the last step
+static void sm_enter(smc_filter* f) { if (f) { (void)hipSetDevice(f->ctx->device); flush_rows(f); } }
+// an island's summary rows, its arrays of step t, and &aux[t] (or null)
+static const double* sm_rows(smc_filter* f, int island) { return f->a.summ + (size_t)island * (f->a.T + 1) * SUMM_STRIDE; }
+static const double* sm_X(smc_filter* f, int island, i64 t) { return f_X(f->a, t) + (size_t)island * f->a.N; }
+static const double* sm_lw(smc_filter* f, int island, i64 t) { return f_lw(f->a, t) + (size_t)island * f->a.N; }
+static const u32* sm_A(smc_filter* f, int island, i64 t) { return f_A(f->a, t) + (size_t)island * f->a.N; }
+static const double* sm_aux(smc_filter* f, i64 t) { return f->a.aux ? f->a.aux + t : nullptr; }
 // cdf = the integer CDF of the weights (lw, row) normalise to
 static void sm_cdf_of(smc_filter* f, const double* lw, const double* row, const SmArgs& s, u64* tot, u64* cdf)
 {
@@ -2099,7 +2094,7 @@ static void sm_cdf_of(smc_filter* f, const double* lw, const double* row, const 
 // cdf = the integer CDF of W_step
 static void sm_weights_cdf(smc_filter* f, int island, i64 step, const SmArgs& s, u64* tot, u64* cdf)
 {
-    sm_cdf_of(f, f_lw(f->a, step) + (size_t)island * f->a.N, sm_rows(f, island) + (size_t)step * SUMM_STRIDE, s, tot, cdf);
+    sm_cdf_of(f, sm_lw(f, island, step), sm_rows(f, island) + (size_t)step * SUMM_STRIDE, s, tot, cdf);
 }
 // last row: M iid draws from W_{t-1} (smoothing.py:278-281), or the caller's indices
 static int sm_last_row(smc_filter* f, int island, SmArgs& s, i64* idx, const int64_t* idx_last_host, const double* d_ulast,
@@ -2121,16 +2116,15 @@ static int sm_last_row(smc_filter* f, int island, SmArgs& s, i64* idx, const int
 // the history pointers of backward step b: X_b, lw_b against the row drawn for step b + 1
 static void sm_step_args(smc_filter* f, int island, i64 b, i64* idx, SmArgs& s)
 {
-    const i64 N = f->a.N;
     const double* rows = sm_rows(f, island);
     s.t = (u32)b;
-    s.Xt = f_X(f->a, b) + (size_t)island * N;
-    s.lwt = f_lw(f->a, b) + (size_t)island * N;
-    s.Xn = f_X(f->a, b + 1) + (size_t)island * N;
-    s.An = f_A(f->a, b + 1) + (size_t)island * N;
+    s.Xt = sm_X(f, island, b);
+    s.lwt = sm_lw(f, island, b);
+    s.Xn = sm_X(f, island, b + 1);
+    s.An = sm_A(f, island, b + 1);
     s.rowt = rows + (size_t)b * SUMM_STRIDE;
     s.rown = rows + (size_t)(b + 1) * SUMM_STRIDE;
-    s.aux = f->a.aux ? f->a.aux + (b + 1) : nullptr;
+    s.aux = sm_aux(f, b + 1);
     s.idx_next = idx + (size_t)(b + 1) * s.M;
     s.idx_out = idx + (size_t)b * s.M;
 }
@@ -2149,23 +2143,47 @@ static int sm_download(smc_filter* f, int island, i64 M, const i64* idx, double*
     SMC_HIP_CHECK(hipStreamSynchronize(st));
     return SMC_OK;
 }
+// The rejection stage of `steps` backward steps: their counters (ctr, a row of SM_CTR_STRIDE per step, the caller zeroes
+// them) and the two lists from the pool, the trials clamped.  u_prop, u_acc, logC and ctr are the caller's, per step.
+static SmRej sm_rej_stage(SmPool& pool, size_t steps, i64 M, int64_t& max_trials, u64** ctr)
+{
+    SmRej r{};
+    pool.get(steps * SM_CTR_STRIDE, ctr);
+    pool.get((size_t)M, &r.listA);
+    pool.get((size_t)M, &r.listB);
+    if (max_trials > SM_REJ_MAX_TRIALS) max_trials = SM_REJ_MAX_TRIALS;    // then the exact draw: still the exact law
+    r.max_trials = max_trials;
+    r.solo = max_trials < sm_reject_solo_trials() ? max_trials : sm_reject_solo_trials();
+    return r;
+}
+// loc[n] = the transition's location at source n (k_os_loc); returns the slot of its scale in the params row
+static int sm_launch_loc(smc_filter* f, const SmArgs& s, double* loc)
+{
+    int slot = 1;
+    sm_with_kind(f->kind, [&](auto k) {
+        SMC_LAUNCH((k_os_loc<decltype(k)::value>), dim3((unsigned)((s.N + SMC_BLOCK - 1) / SMC_BLOCK)), dim3(SMC_BLOCK),
+                   f->ctx->stream, s, loc);
+        slot = sm_scale_slot<decltype(k)::value>();
+    });
+    return slot;
+}
 
 int smc_filter_backward_sample(smc_filter* f, int island, int method, int64_t M, int nsteps, uint64_t seed,
                                const int64_t* idx_last_host, const double* u_last_host,
                                const double* u_host, const double* u_acc_host,
                                int64_t* idx_out_host, double* paths_out_host)
 {
-    if (f) { (void)hipSetDevice(f->ctx->device); flush_rows(f); }
-    int rc = sm_check_filter(__func__, f, island, idx_out_host);
-    if (rc != SMC_OK) return rc;
+    sm_enter(f);
+    const char* bad = sm_check_filter(f, island, idx_out_host);
+    SMC_REQUIRE(!bad, bad);
     SMC_REQUIRE(method == SMC_BACKWARD_ON2 || method == SMC_BACKWARD_MCMC, "unknown method");
-    if ((rc = sm_check_trajectories(__func__, f, M)) != SMC_OK) return rc;
+    SMC_REQUIRE(M >= 1 && M < ((int64_t)1 << 31), "M must be at least 1 (and below 2^31)");
     SMC_REQUIRE(nsteps >= 1, "nsteps must be at least 1");
     const i64 t = f->t_host, N = f->a.N;
-    if ((rc = sm_check_steps(__func__, f)) != SMC_OK) return rc;
+    SMC_REQUIRE(f->t_host >= 1, "no step has run yet");
     if (method == SMC_BACKWARD_ON2) nsteps = 1;
     SMC_REQUIRE((i64)nsteps * M < ((i64)1 << 32), "nsteps * M must stay below 2^32 (Philox counter)");
-    if ((rc = sm_check_idx_last(__func__, f, M, idx_last_host)) != SMC_OK) return rc;
+    SMC_REQUIRE(!(bad = sm_check_idx_last(f, M, idx_last_host)), bad);
     hipStream_t st = f->ctx->stream;
     SmPool pool(f->ctx);
     const bool mcmc = method == SMC_BACKWARD_MCMC;
@@ -2174,14 +2192,14 @@ int smc_filter_backward_sample(smc_filter* f, int island, int method, int64_t M,
     i64* idx = nullptr;
     u64 *cdf = nullptr, *tot = nullptr;
     double *paths = nullptr, *d_ulast = nullptr, *d_u = nullptr, *d_uacc = nullptr;
-    rc = pool.get((size_t)t * M, &idx);
-    if (rc == SMC_OK && need_cdf) rc = pool.get((size_t)N, &cdf);
-    if (rc == SMC_OK && need_cdf) rc = pool.get((size_t)nch, &tot);
-    if (rc == SMC_OK && paths_out_host) rc = pool.get((size_t)t * M, &paths);
-    if (rc == SMC_OK && !idx_last_host) rc = pool.upload(u_last_host, (size_t)M, &d_ulast);
     const size_t per_step = (size_t)nsteps * M;
-    if (rc == SMC_OK) rc = pool.upload(u_host, (size_t)(t - 1) * per_step, &d_u);
-    if (rc == SMC_OK && mcmc) rc = pool.upload(u_acc_host, (size_t)(t - 1) * per_step, &d_uacc);
+    pool.get((size_t)t * M, &idx);
+    if (need_cdf) { pool.get((size_t)N, &cdf); pool.get((size_t)nch, &tot); }
+    if (paths_out_host) pool.get((size_t)t * M, &paths);
+    if (!idx_last_host) pool.upload(u_last_host, (size_t)M, &d_ulast);
+    pool.upload(u_host, (size_t)(t - 1) * per_step, &d_u);
+    if (mcmc) pool.upload(u_acc_host, (size_t)(t - 1) * per_step, &d_uacc);
+    int rc = pool.status();
     if (rc != SMC_OK) return rc;
     SMC_HIP_CHECK(hipMemsetAsync(idx, 0, (size_t)t * M * 8, st));          // (every index a kernel reads is in range)
 
@@ -2193,13 +2211,10 @@ int smc_filter_backward_sample(smc_filter* f, int island, int method, int64_t M,
         sm_step_args(f, island, b, idx, s);
         s.u = d_u ? d_u + (size_t)b * per_step : nullptr;
         s.u_acc = d_uacc ? d_uacc + (size_t)b * per_step : nullptr;
-        switch (f->kind) {
-        case SMC_MODEL_LINGAUSS: sm_launch_step<SMC_MODEL_LINGAUSS>(method, st, s); break;
-        case SMC_MODEL_STOCHVOL: sm_launch_step<SMC_MODEL_STOCHVOL>(method, st, s); break;
-        case SMC_MODEL_GORDON: sm_launch_step<SMC_MODEL_GORDON>(method, st, s); break;
-        case SMC_MODEL_THETALOGISTIC: sm_launch_step<SMC_MODEL_THETALOGISTIC>(method, st, s); break;
-        default: sm_launch_step<SMC_MODEL_DISCRETECOX>(method, st, s); break;
-        }
+        sm_with_kind(f->kind, [&](auto k) {
+            if (mcmc) SMC_LAUNCH((k_sm_mcmc<decltype(k)::value>), dim3((unsigned)((M + SMC_BLOCK - 1) / SMC_BLOCK)), dim3(SMC_BLOCK), st, s);
+            else SMC_LAUNCH((k_sm_on2<decltype(k)::value>), dim3((unsigned)M), dim3(SMC_BLOCK), st, s);
+        });
     }
     return sm_download(f, island, M, idx, paths, idx_out_host, paths_out_host);
 }
@@ -2210,10 +2225,10 @@ int smc_filter_backward_sample(smc_filter* f, int island, int method, int64_t M,
 int smc_filter_csmc_paths(smc_filter* f, int backward, uint64_t seed, const double* u_last_host, const double* u_host,
                           int64_t* idx_out_host, double* paths_out_host, double* paths_out_dev)
 {
-    if (f) { (void)hipSetDevice(f->ctx->device); flush_rows(f); }
+    sm_enter(f);
     SMC_REQUIRE(f && (idx_out_host || paths_out_host || paths_out_dev), "null filter, or no output asked for");
     SMC_REQUIRE(!f->plan.sqmc(), "SQMC filters are not supported");
-    SMC_REQUIRE(csmc_kind_ok(f->kind), "model kind is not supported: LINGAUSS, STOCHVOL, GORDON, THETALOGISTIC, DISCRETECOX");
+    SMC_REQUIRE(sm_kind_ok(f->kind), "model kind is not supported: LINGAUSS, STOCHVOL, GORDON, THETALOGISTIC, DISCRETECOX");
     SMC_REQUIRE(f->a.hist == 1, "the filter was created without a whole history (keep_history = 1)");
     SMC_REQUIRE(f->a.N <= F_TILE, "N <= 1024: one workgroup walks an island's history");
     SMC_REQUIRE(f->t_host >= 1, "no step has run yet");
@@ -2223,30 +2238,22 @@ int smc_filter_csmc_paths(smc_filter* f, int backward, uint64_t seed, const doub
     SmPool pool(f->ctx);
     i64* idx = nullptr;
     double *paths = paths_out_dev, *d_ulast = nullptr, *d_u = nullptr;
-    int rc = pool.get(C * t, &idx);
-    if (rc == SMC_OK && !paths) rc = pool.get(C * t, &paths);
-    if (rc == SMC_OK) rc = pool.upload(u_last_host, C, &d_ulast);
-    if (rc == SMC_OK && backward) rc = pool.upload(u_host, (size_t)(t - 1) * C, &d_u);
-    if (rc != SMC_OK) return rc;
+    pool.get(C * t, &idx);
+    if (!paths) pool.get(C * t, &paths);
+    pool.upload(u_last_host, C, &d_ulast);
+    if (backward) pool.upload(u_host, (size_t)(t - 1) * C, &d_u);
+    if (pool.status() != SMC_OK) return pool.status();
     const dim3 grid(1, f->a.n_islands);
     const int kform = f->plan.two_level ? 1 : 0, bw = backward ? 1 : 0;
-#define CP_CASE(KINDV)                                                                                                   \
-    case KINDV:                                                                                                          \
-        if (f->a.N <= 256)                                                                                               \
-            SMC_LAUNCH((k_csmc_path<KINDV, 64>), grid, dim3(64), st, f->a, t, bw, kform, (u64)seed, (const double*)d_ulast, \
-                       (const double*)d_u, idx, paths);                                                                  \
-        else                                                                                                             \
-            SMC_LAUNCH((k_csmc_path<KINDV, SMC_BLOCK>), grid, dim3(SMC_BLOCK), st, f->a, t, bw, kform, (u64)seed,        \
-                       (const double*)d_ulast, (const double*)d_u, idx, paths);                                          \
-        break;
-    switch (f->kind) {
-        CP_CASE(SMC_MODEL_LINGAUSS)
-        CP_CASE(SMC_MODEL_STOCHVOL)
-        CP_CASE(SMC_MODEL_GORDON)
-        CP_CASE(SMC_MODEL_THETALOGISTIC)
-        CP_CASE(SMC_MODEL_DISCRETECOX)
-    }
-#undef CP_CASE
+    sm_with_kind(f->kind, [&](auto k) {
+        constexpr int KIND = decltype(k)::value;
+        if (f->a.N <= 256)
+            SMC_LAUNCH((k_csmc_path<KIND, 64>), grid, dim3(64), st, f->a, t, bw, kform, (u64)seed, (const double*)d_ulast,
+                       (const double*)d_u, idx, paths);
+        else
+            SMC_LAUNCH((k_csmc_path<KIND, SMC_BLOCK>), grid, dim3(SMC_BLOCK), st, f->a, t, bw, kform, (u64)seed,
+                       (const double*)d_ulast, (const double*)d_u, idx, paths);
+    });
     SMC_LAUNCH_CHECK();
     if (idx_out_host) SMC_HIP_CHECK(hipMemcpyAsync(idx_out_host, idx, C * t * 8, hipMemcpyDeviceToHost, st));
     if (paths_out_host) SMC_HIP_CHECK(hipMemcpyAsync(paths_out_host, paths, C * t * 8, hipMemcpyDeviceToHost, st));
@@ -2265,47 +2272,40 @@ int smc_filter_backward_reject(smc_filter* f, int island, int64_t M, int64_t max
                                int64_t* idx_out_host, double* paths_out_host,
                                int64_t* nprops_out_host, int64_t* nexact_out_host)
 {
-    if (f) { (void)hipSetDevice(f->ctx->device); flush_rows(f); }
-    int rc = sm_check_filter(__func__, f, island, idx_out_host);
-    if (rc != SMC_OK) return rc;
-    if ((rc = sm_check_trajectories(__func__, f, M)) != SMC_OK) return rc;
+    sm_enter(f);
+    const char* bad = sm_check_filter(f, island, idx_out_host);
+    SMC_REQUIRE(!bad, bad);
+    SMC_REQUIRE(M >= 1 && M < ((int64_t)1 << 31), "M must be at least 1 (and below 2^31)");
     SMC_REQUIRE(max_trials >= 1, "max_trials must be at least 1");
-    if ((rc = sm_check_steps(__func__, f)) != SMC_OK) return rc;
+    SMC_REQUIRE(f->t_host >= 1, "no step has run yet");
     const i64 t = f->t_host, N = f->a.N;
     SMC_REQUIRE(t < 2 || log_bound_host, "null log_bound: the bounds log C_s, s = 1 .. t - 1, are the caller's");
-    if ((rc = sm_check_idx_last(__func__, f, M, idx_last_host)) != SMC_OK) return rc;
-    if (max_trials > SM_REJ_MAX_TRIALS) max_trials = SM_REJ_MAX_TRIALS;    // then the exact draw: still the exact law
+    SMC_REQUIRE(!(bad = sm_check_idx_last(f, M, idx_last_host)), bad);
     hipStream_t st = f->ctx->stream;
     SmPool pool(f->ctx);
     const unsigned nch = (unsigned)((N + SM_CHUNK - 1) / SM_CHUNK);
     const size_t nb = (size_t)(t - 1);                                       // backward steps
     i64* idx = nullptr;
     u64 *cdf = nullptr, *tot = nullptr, *ctr = nullptr;
-    u32 *listA = nullptr, *listB = nullptr;
     double *paths = nullptr, *d_ulast = nullptr, *d_u = nullptr, *d_uprop = nullptr, *d_uacc = nullptr, *d_logC = nullptr;
-    rc = pool.get((size_t)t * M, &idx);
-    if (rc == SMC_OK) rc = pool.get((size_t)N, &cdf);
-    if (rc == SMC_OK) rc = pool.get((size_t)nch, &tot);
-    if (rc == SMC_OK) rc = pool.get(nb * SM_CTR_STRIDE, &ctr);
-    if (rc == SMC_OK) rc = pool.get((size_t)M, &listA);
-    if (rc == SMC_OK) rc = pool.get((size_t)M, &listB);
-    if (rc == SMC_OK && paths_out_host) rc = pool.get((size_t)t * M, &paths);
-    if (rc == SMC_OK && !idx_last_host) rc = pool.upload(u_last_host, (size_t)M, &d_ulast);
+    pool.get((size_t)t * M, &idx);
+    pool.get((size_t)N, &cdf);
+    pool.get((size_t)nch, &tot);
+    SmRej r = sm_rej_stage(pool, nb, M, max_trials, &ctr);
+    if (paths_out_host) pool.get((size_t)t * M, &paths);
+    if (!idx_last_host) pool.upload(u_last_host, (size_t)M, &d_ulast);
     const size_t per_step = (size_t)max_trials * M;
-    if (rc == SMC_OK && nb) rc = pool.upload(log_bound_host, nb, &d_logC);
-    if (rc == SMC_OK) rc = pool.upload(u_host, nb * M, &d_u);
-    if (rc == SMC_OK) rc = pool.upload(u_prop_host, nb * per_step, &d_uprop);
-    if (rc == SMC_OK) rc = pool.upload(u_acc_host, nb * per_step, &d_uacc);
+    if (nb) pool.upload(log_bound_host, nb, &d_logC);
+    pool.upload(u_host, nb * M, &d_u);
+    pool.upload(u_prop_host, nb * per_step, &d_uprop);
+    pool.upload(u_acc_host, nb * per_step, &d_uacc);
+    int rc = pool.status();
     if (rc != SMC_OK) return rc;
     SMC_HIP_CHECK(hipMemsetAsync(idx, 0, (size_t)t * M * 8, st));          // (every index a kernel reads is in range)
     SMC_HIP_CHECK(hipMemsetAsync(ctr, 0, (nb ? nb : 1) * SM_CTR_STRIDE * 8, st));
 
     SmArgs s = sm_args(f, island, M, seed, cdf);
     if ((rc = sm_last_row(f, island, s, idx, idx_last_host, d_ulast, tot, cdf)) != SMC_OK) return rc;
-    SmRej r{};
-    r.listA = listA; r.listB = listB;
-    r.max_trials = max_trials;
-    r.solo = max_trials < sm_reject_solo_trials() ? max_trials : sm_reject_solo_trials();
     for (i64 b = t - 2; b >= 0; --b) {
         sm_weights_cdf(f, island, b, s, tot, cdf);
         sm_step_args(f, island, b, idx, s);
@@ -2314,13 +2314,7 @@ int smc_filter_backward_reject(smc_filter* f, int island, int64_t M, int64_t max
         r.u_acc = d_uacc ? d_uacc + (size_t)b * per_step : nullptr;
         r.logC = d_logC + b;
         r.ctr = ctr + (size_t)b * SM_CTR_STRIDE;
-        switch (f->kind) {
-        case SMC_MODEL_LINGAUSS: sm_launch_reject<SMC_MODEL_LINGAUSS>(st, s, r); break;
-        case SMC_MODEL_STOCHVOL: sm_launch_reject<SMC_MODEL_STOCHVOL>(st, s, r); break;
-        case SMC_MODEL_GORDON: sm_launch_reject<SMC_MODEL_GORDON>(st, s, r); break;
-        case SMC_MODEL_THETALOGISTIC: sm_launch_reject<SMC_MODEL_THETALOGISTIC>(st, s, r); break;
-        default: sm_launch_reject<SMC_MODEL_DISCRETECOX>(st, s, r); break;
-        }
+        sm_with_kind(f->kind, [&](auto k) { sm_launch_reject<decltype(k)::value>(st, s, r); });
     }
     std::vector<u64> counts(nb * SM_CTR_STRIDE);
     if (nb && (nprops_out_host || nexact_out_host))
@@ -2336,26 +2330,105 @@ int smc_filter_backward_reject(smc_filter* f, int island, int64_t M, int64_t max
 // On-line smoothing (smc_online.h): one update behind the step just run.  Stateless: Phi, X_{t-1} and lw_{t-1} are the
 // caller's device arrays, everything else is read from the filter's current step or lives in pool workspaces for the
 // duration of the call.  One synchronisation: the download of the K estimates (and what else was asked for).
+struct OsParis {                       // the PaRIS draw of one call
+    int n_paris;                       // indices per target; 0: no draw (SMC_ONLINE_NAIVE)
+    int64_t max_trials;
+    double log_bound;
+    const double *u_prop, *u_acc, *u;  // the caller's tapes (host) or null
+    i64* idx;                          // (N n_paris) the drawn indices
+    u64* ctr;                          // the draw's counters (both: for the download)
+};
+// t == 0: Phi_0 = psi_0(X_0)
+static int os_init(smc_filter* f, const OsPsi& psi, const double* X, double* Phi_dev)
+{
+    SMC_LAUNCH(k_os_init, dim3((unsigned)((f->a.N + SMC_BLOCK - 1) / SMC_BLOCK)), dim3(SMC_BLOCK), f->ctx->stream, psi, X, f->a.N,
+               Phi_dev);
+    return SMC_OK;
+}
+// SMC_ONLINE_ON2: all pairs, by source slices; s holds the step (Xt, lwt: the previous particles, Xn: the current ones)
+static int os_update_on2(smc_filter* f, SmPool& pool, const SmArgs& s, const OsPsi& psi, double* Phi_dev)
+{
+    const i64 N = s.N;
+    const int K = psi.K, KP = K == 1 ? 1 : K <= 4 ? 4 : 8, nslices = os_slices(N);
+    hipStream_t st = f->ctx->stream;
+    double *loc = nullptr, *part = nullptr;
+    pool.get((size_t)N, &loc);
+    pool.get((size_t)nslices * N * OS_PART(KP), &part);
+    if (pool.status() != SMC_OK) return pool.status();
+    OsOn2 o{};
+    o.X = s.Xn; o.Xprev = s.Xt; o.lwprev = s.lwt; o.loc = loc; o.Phi = Phi_dev;
+    o.part = part; o.p = s.p; o.slot = sm_launch_loc(f, s, loc); o.N = N; o.K = K;
+    const i64 ntile = (N + OS_TILE - 1) / OS_TILE;
+    o.per_slice = ((ntile + nslices - 1) / nslices) * OS_TILE;
+    const int used = (int)((N + o.per_slice - 1) / o.per_slice);            // (no empty slice is launched or merged)
+    // (the merge reads every partial before it writes a target's Phi, and k_os_on2 is done: Phi_dev in place)
+    if (KP == 1) os_launch_on2<1>(st, o, used, psi, Phi_dev);
+    else if (KP == 4) os_launch_on2<4>(st, o, used, psi, Phi_dev);
+    else os_launch_on2<8>(st, o, used, psi, Phi_dev);
+    return SMC_OK;
+}
+// SMC_ONLINE_PARIS: d.n_paris indices per target by rejection, the targets of s.idx_next drawing from W_{t-1}
+static int os_paris_draw(smc_filter* f, SmPool& pool, SmArgs& s, OsParis& d)
+{
+    const i64 N = s.N, M = s.M;
+    hipStream_t st = f->ctx->stream;
+    const unsigned nch = (unsigned)((N + SM_CHUNK - 1) / SM_CHUNK);
+    u64 *cdf = nullptr, *tot = nullptr;
+    i64* targets = nullptr;
+    double *d_u = nullptr, *d_uprop = nullptr, *d_uacc = nullptr, *d_logC = nullptr;
+    pool.get((size_t)N, &cdf);
+    pool.get((size_t)nch, &tot);
+    SmRej r = sm_rej_stage(pool, 1, M, d.max_trials, &d.ctr);
+    pool.get((size_t)M, &targets);
+    pool.get((size_t)M, &d.idx);
+    pool.upload(&d.log_bound, 1, &d_logC);
+    pool.upload(d.u, (size_t)M, &d_u);
+    pool.upload(d.u_prop, (size_t)d.max_trials * M, &d_uprop);
+    pool.upload(d.u_acc, (size_t)d.max_trials * M, &d_uacc);
+    if (pool.status() != SMC_OK) return pool.status();
+    SMC_HIP_CHECK(hipMemsetAsync(d.idx, 0, (size_t)M * 8, st));                // (every index a kernel reads is in range)
+    SMC_HIP_CHECK(hipMemsetAsync(d.ctr, 0, SM_CTR_STRIDE * 8, st));
+    SMC_LAUNCH(k_os_targets, dim3((unsigned)((M + SMC_BLOCK - 1) / SMC_BLOCK)), dim3(SMC_BLOCK), st, M, d.n_paris, targets);
+    s.cdf = cdf;
+    sm_cdf_of(f, s.lwt, s.rowt, s, tot, cdf);
+    s.u = d_u; s.idx_next = targets; s.idx_out = d.idx;
+    r.u_prop = d_uprop; r.u_acc = d_uacc; r.logC = d_logC; r.ctr = d.ctr;
+    sm_with_kind(f->kind, [&](auto k) { sm_launch_reject<decltype(k)::value>(st, s, r); });
+    return SMC_OK;
+}
+// SMC_ONLINE_NAIVE, SMC_ONLINE_PARIS: Phi gathered along the ancestors, or the drawn indices (d.n_paris of them)
+static int os_update_gather(smc_filter* f, SmPool& pool, SmArgs& s, const OsPsi& psi, double* Phi_dev, OsParis& d)
+{
+    const i64 N = s.N;
+    hipStream_t st = f->ctx->stream;
+    double* Phi_new = nullptr;
+    pool.get((size_t)N * psi.K, &Phi_new);
+    const int rc = d.n_paris ? os_paris_draw(f, pool, s, d) : pool.status();
+    if (rc != SMC_OK) return rc;
+    SMC_LAUNCH(k_os_gather, dim3((unsigned)((N + SMC_BLOCK - 1) / SMC_BLOCK)), dim3(SMC_BLOCK), st, psi, s.Xn, s.Xt,
+               (const double*)Phi_dev, s.An, s.rown, (const i64*)d.idx, d.n_paris, N, Phi_new);
+    SMC_HIP_CHECK(hipMemcpyAsync(Phi_dev, Phi_new, (size_t)N * psi.K * 8, hipMemcpyDeviceToDevice, st));
+    return SMC_OK;
+}
 int smc_filter_online_smooth(smc_filter* f, int island, int method, const smc_addfunc* psi_host,
                              double* Phi_dev, double* Xprev_dev, double* lwprev_dev,
                              int n_paris, int64_t max_trials, uint64_t seed, double log_bound,
                              const double* u_prop_host, const double* u_acc_host, const double* u_host,
                              int64_t* idx_out_host, int64_t* nprop_out, double* est_out_host)
 {
-    if (f) { (void)hipSetDevice(f->ctx->device); flush_rows(f); }
-    int rc = sm_check_filter(__func__, f, island, est_out_host, false);
-    if (rc != SMC_OK) return rc;
+    sm_enter(f);
+    const char* bad = sm_check_filter(f, island, est_out_host, false);
+    SMC_REQUIRE(!bad, bad);
     SMC_REQUIRE(psi_host && Phi_dev && Xprev_dev && lwprev_dev, "null argument");
     SMC_REQUIRE(psi_host->K >= 1 && psi_host->K <= OS_KMAX, "K must be 1 .. 8");
     SMC_REQUIRE(method == SMC_ONLINE_NAIVE || method == SMC_ONLINE_ON2 || method == SMC_ONLINE_PARIS, "unknown method");
-    if ((rc = sm_check_steps(__func__, f)) != SMC_OK) return rc;
+    SMC_REQUIRE(f->t_host >= 1, "no step has run yet");
     const bool paris = method == SMC_ONLINE_PARIS;
     const i64 N = f->a.N, t = f->t_host - 1;
     if (paris) {
         SMC_REQUIRE(n_paris >= 1, "n_paris must be at least 1");
         SMC_REQUIRE(max_trials >= 1, "max_trials must be at least 1");
         SMC_REQUIRE(N * (i64)n_paris < ((i64)1 << 31), "N n_paris must stay below 2^31");
-        if (max_trials > SM_REJ_MAX_TRIALS) max_trials = SM_REJ_MAX_TRIALS;
     }
     OsPsi psi{};
     const int K = psi.K = psi_host->K;
@@ -2363,104 +2436,30 @@ int smc_filter_online_smooth(smc_filter* f, int island, int method, const smc_ad
     memcpy(psi.c, psi_host->c, sizeof psi.c);
     hipStream_t st = f->ctx->stream;
     SmPool pool(f->ctx);
-    const unsigned nblk = (unsigned)((N + SMC_BLOCK - 1) / SMC_BLOCK);
     const int nest = (int)((N + OS_EST_CHUNK - 1) / OS_EST_CHUNK);
-    const double* X = f_X(f->a, t) + (size_t)island * N;
-    const double* lw = f_lw(f->a, t) + (size_t)island * N;
+    const double *X = sm_X(f, island, t), *lw = sm_lw(f, island, t);
     const double* rows = sm_rows(f, island);
     const double* row = rows + (size_t)t * SUMM_STRIDE;
     double *est = nullptr, *epart = nullptr;
-    rc = pool.get((size_t)OS_KMAX, &est);
-    if (rc == SMC_OK) rc = pool.get((size_t)nest * OS_KMAX, &epart);
+    pool.get((size_t)OS_KMAX, &est);
+    pool.get((size_t)nest * OS_KMAX, &epart);
+    int rc = pool.status();
     if (rc != SMC_OK) return rc;
-    const i64 M = paris ? N * n_paris : 0;
-    i64* idx = nullptr;
-    u64* ctr = nullptr;
+    OsParis d{paris ? n_paris : 0, max_trials, log_bound, u_prop_host, u_acc_host, u_host, nullptr, nullptr};
+    const i64 M = N * d.n_paris;
     if (t == 0) {
-        SMC_LAUNCH(k_os_init, dim3(nblk), dim3(SMC_BLOCK), st, psi, X, N, Phi_dev);
+        rc = os_init(f, psi, X, Phi_dev);
     } else {
         SmArgs s = sm_args(f, island, M, seed, nullptr);
         s.t = (u32)(t - 1);
         s.Xt = Xprev_dev; s.lwt = lwprev_dev; s.Xn = X;
-        s.An = f_A(f->a, t) + (size_t)island * N;
+        s.An = sm_A(f, island, t);
         s.rowt = rows + (size_t)(t - 1) * SUMM_STRIDE;
         s.rown = row;
-        s.aux = f->a.aux ? f->a.aux + t : nullptr;
-        double* Phi_new = nullptr;
-        if (method == SMC_ONLINE_ON2) {
-            const int nslices = os_slices(N);
-            const int KP = K == 1 ? 1 : K <= 4 ? 4 : 8;
-            double *loc = nullptr, *part = nullptr;
-            rc = pool.get((size_t)N, &loc);
-            if (rc == SMC_OK) rc = pool.get((size_t)nslices * N * OS_PART(KP), &part);
-            if (rc != SMC_OK) return rc;
-            int slot = 1;
-            switch (f->kind) {
-            case SMC_MODEL_LINGAUSS: os_launch_loc<SMC_MODEL_LINGAUSS>(st, s, loc); slot = sm_scale_slot<SMC_MODEL_LINGAUSS>(); break;
-            case SMC_MODEL_STOCHVOL: os_launch_loc<SMC_MODEL_STOCHVOL>(st, s, loc); slot = sm_scale_slot<SMC_MODEL_STOCHVOL>(); break;
-            case SMC_MODEL_GORDON: os_launch_loc<SMC_MODEL_GORDON>(st, s, loc); slot = sm_scale_slot<SMC_MODEL_GORDON>(); break;
-            case SMC_MODEL_THETALOGISTIC:
-                os_launch_loc<SMC_MODEL_THETALOGISTIC>(st, s, loc); slot = sm_scale_slot<SMC_MODEL_THETALOGISTIC>(); break;
-            default: os_launch_loc<SMC_MODEL_DISCRETECOX>(st, s, loc); slot = sm_scale_slot<SMC_MODEL_DISCRETECOX>(); break;
-            }
-            OsOn2 o{};
-            o.X = X; o.Xprev = Xprev_dev; o.lwprev = lwprev_dev; o.loc = loc; o.Phi = Phi_dev;
-            o.part = part; o.p = s.p; o.slot = slot; o.N = N; o.K = K;
-            const i64 ntile = (N + OS_TILE - 1) / OS_TILE;
-            o.per_slice = ((ntile + nslices - 1) / nslices) * OS_TILE;
-            const int used = (int)((N + o.per_slice - 1) / o.per_slice);            // (no empty slice is launched or merged)
-            // (the merge reads every partial before it writes a target's Phi, and k_os_on2 is done: Phi_dev in place)
-            if (KP == 1) os_launch_on2<1>(st, o, used, psi, Phi_dev);
-            else if (KP == 4) os_launch_on2<4>(st, o, used, psi, Phi_dev);
-            else os_launch_on2<8>(st, o, used, psi, Phi_dev);
-        } else {
-            if ((rc = pool.get((size_t)N * K, &Phi_new)) != SMC_OK) return rc;
-            if (paris) {
-                const unsigned nch = (unsigned)((N + SM_CHUNK - 1) / SM_CHUNK);
-                u64 *cdf = nullptr, *tot = nullptr;
-                u32 *listA = nullptr, *listB = nullptr;
-                i64* targets = nullptr;
-                double *d_u = nullptr, *d_uprop = nullptr, *d_uacc = nullptr, *d_logC = nullptr;
-                rc = pool.get((size_t)N, &cdf);
-                if (rc == SMC_OK) rc = pool.get((size_t)nch, &tot);
-                if (rc == SMC_OK) rc = pool.get((size_t)SM_CTR_STRIDE, &ctr);
-                if (rc == SMC_OK) rc = pool.get((size_t)M, &listA);
-                if (rc == SMC_OK) rc = pool.get((size_t)M, &listB);
-                if (rc == SMC_OK) rc = pool.get((size_t)M, &targets);
-                if (rc == SMC_OK) rc = pool.get((size_t)M, &idx);
-                if (rc == SMC_OK) rc = pool.upload(&log_bound, 1, &d_logC);
-                if (rc == SMC_OK) rc = pool.upload(u_host, (size_t)M, &d_u);
-                if (rc == SMC_OK) rc = pool.upload(u_prop_host, (size_t)max_trials * M, &d_uprop);
-                if (rc == SMC_OK) rc = pool.upload(u_acc_host, (size_t)max_trials * M, &d_uacc);
-                if (rc != SMC_OK) return rc;
-                SMC_HIP_CHECK(hipMemsetAsync(idx, 0, (size_t)M * 8, st));              // (every index a kernel reads is in range)
-                SMC_HIP_CHECK(hipMemsetAsync(ctr, 0, SM_CTR_STRIDE * 8, st));
-                SMC_LAUNCH(k_os_targets, dim3((unsigned)((M + SMC_BLOCK - 1) / SMC_BLOCK)), dim3(SMC_BLOCK), st, M, n_paris, targets);
-                s.cdf = cdf;
-                sm_cdf_of(f, lwprev_dev, s.rowt, s, tot, cdf);
-                s.u = d_u;
-                s.idx_next = targets;
-                s.idx_out = idx;
-                SmRej r{};
-                r.listA = listA; r.listB = listB;
-                r.max_trials = max_trials;
-                r.solo = max_trials < sm_reject_solo_trials() ? max_trials : sm_reject_solo_trials();
-                r.u_prop = d_uprop; r.u_acc = d_uacc;
-                r.logC = d_logC;
-                r.ctr = ctr;
-                switch (f->kind) {
-                case SMC_MODEL_LINGAUSS: sm_launch_reject<SMC_MODEL_LINGAUSS>(st, s, r); break;
-                case SMC_MODEL_STOCHVOL: sm_launch_reject<SMC_MODEL_STOCHVOL>(st, s, r); break;
-                case SMC_MODEL_GORDON: sm_launch_reject<SMC_MODEL_GORDON>(st, s, r); break;
-                case SMC_MODEL_THETALOGISTIC: sm_launch_reject<SMC_MODEL_THETALOGISTIC>(st, s, r); break;
-                default: sm_launch_reject<SMC_MODEL_DISCRETECOX>(st, s, r); break;
-                }
-            }
-            SMC_LAUNCH(k_os_gather, dim3(nblk), dim3(SMC_BLOCK), st, psi, X, (const double*)Xprev_dev, (const double*)Phi_dev,
-                       s.An, row, (const i64*)idx, paris ? n_paris : 0, N, Phi_new);
-            SMC_HIP_CHECK(hipMemcpyAsync(Phi_dev, Phi_new, (size_t)N * K * 8, hipMemcpyDeviceToDevice, st));
-        }
+        s.aux = sm_aux(f, t);
+        rc = method == SMC_ONLINE_ON2 ? os_update_on2(f, pool, s, psi, Phi_dev) : os_update_gather(f, pool, s, psi, Phi_dev, d);
     }
+    if (rc != SMC_OK) return rc;
     SMC_LAUNCH(k_os_est_partials, dim3((unsigned)nest), dim3(SMC_BLOCK), st, lw, row, (const double*)Phi_dev, N, K,
                f->plan.two_level ? 1 : 0, epart);
     SMC_LAUNCH(k_os_est_final, dim3(1), dim3(64), st, (const double*)epart, nest, K, est);
@@ -2468,8 +2467,8 @@ int smc_filter_online_smooth(smc_filter* f, int island, int method, const smc_ad
     SMC_HIP_CHECK(hipMemcpyAsync(Xprev_dev, X, (size_t)N * 8, hipMemcpyDeviceToDevice, st));
     SMC_HIP_CHECK(hipMemcpyAsync(lwprev_dev, lw, (size_t)N * 8, hipMemcpyDeviceToDevice, st));
     u64 counts[SM_CTR_STRIDE] = {0, 0, 0, 0};
-    if (ctr && nprop_out) SMC_HIP_CHECK(hipMemcpyAsync(counts, ctr, sizeof counts, hipMemcpyDeviceToHost, st));
-    if (idx && idx_out_host) SMC_HIP_CHECK(hipMemcpyAsync(idx_out_host, idx, (size_t)M * 8, hipMemcpyDeviceToHost, st));
+    if (d.ctr && nprop_out) SMC_HIP_CHECK(hipMemcpyAsync(counts, d.ctr, sizeof counts, hipMemcpyDeviceToHost, st));
+    if (d.idx && idx_out_host) SMC_HIP_CHECK(hipMemcpyAsync(idx_out_host, d.idx, (size_t)M * 8, hipMemcpyDeviceToHost, st));
     SMC_HIP_CHECK(hipMemcpyAsync(est_out_host, est, (size_t)K * 8, hipMemcpyDeviceToHost, st));
     SMC_HIP_CHECK(hipStreamSynchronize(st));
     if (nprop_out) *nprop_out = (int64_t)counts[SM_CTR_NPROPS];
@@ -2479,6 +2478,80 @@ int smc_filter_online_smooth(smc_filter* f, int island, int method, const smc_ad
 // Two-filter smoothing (smc_twofilter.h).  Reads both filters only; workspaces from the pool, launches on the context's
 // stream (the two filters share it: one stream orders the call).  One synchronisation: the download of the estimates,
 // the ESS and, when asked for, the pair indices.
+struct TfWork {                        // what the two item functions share
+    const double* Xi;                  // (Ni) the information filter's particles
+    double *lwi, *bmaxi;               // (Ni) their log-weights less log gamma plus modif_info; the block maxima of those
+    double *gmax, *items;              // 3 maxima: of the items, and one for each CDF of the sampled pairs; (nitems, K + 2)
+    double *d_mf, *d_mi;               // modif_forward, modif_info on the device or null
+    i64 Ni;
+};
+// SMC_TWOFILTER_ON2: one item per particle of the information filter, all forward particles summed over in slices
+static int tf_items_on2(smc_filter* f, SmPool& pool, const SmArgs& s, const OsPsi& psi, const TfWork& w)
+{
+    const i64 Ni = w.Ni, Nf = s.N;
+    const unsigned nbi = (unsigned)((Ni + SMC_BLOCK - 1) / SMC_BLOCK);
+    const int nslices = tf_slices(Ni, Nf);
+    hipStream_t st = f->ctx->stream;
+    double *loc = nullptr, *part = nullptr;
+    pool.get((size_t)Nf, &loc);
+    pool.get((size_t)nslices * Ni * 4, &part);
+    if (pool.status() != SMC_OK) return pool.status();
+    TfOn2 o{};
+    o.Xi = w.Xi; o.Xf = s.Xt; o.lwf = s.lwt; o.loc = loc; o.part = part; o.p = s.p; o.slot = sm_launch_loc(f, s, loc);
+    o.Ni = Ni; o.Nf = Nf;
+    const i64 ntile = (Nf + SMC_BLOCK - 1) / SMC_BLOCK;
+    o.per_slice = ((ntile + nslices - 1) / nslices) * SMC_BLOCK;
+    const int used = (int)((Nf + o.per_slice - 1) / o.per_slice);               // (no empty slice is launched or merged)
+    SMC_LAUNCH(k_tf_on2, dim3(nbi, (unsigned)used), dim3(SMC_BLOCK), st, o);
+    SMC_LAUNCH(k_tf_merge, dim3(nbi), dim3(SMC_BLOCK), st, psi, w.Xi, (const double*)w.lwi, (const double*)part, used, Ni, w.items);
+    return SMC_OK;
+}
+// SMC_TWOFILTER_ON: one item per pair (J, I) -- the caller's, or drawn from the two (modified) weight vectors.  q.J and
+// q.I stay for the download.
+static int tf_items_pairs(smc_filter* f, int island, SmPool& pool, const SmArgs& s, const OsPsi& psi, const TfWork& w,
+                          const int64_t* idx_fwd_host, const int64_t* idx_info_host, const double* u_fwd_host,
+                          const double* u_info_host, TfPairs& q)
+{
+    const i64 Ni = w.Ni, Nf = s.N, P = s.M;
+    const bool given = idx_fwd_host || idx_info_host;
+    hipStream_t st = f->ctx->stream;
+    const i64 Nmax = Nf > Ni ? Nf : Ni;
+    const unsigned nbf = (unsigned)((Nf + SMC_BLOCK - 1) / SMC_BLOCK);
+    i64 *J_in = nullptr, *I_in = nullptr;
+    u64 *cdf_f = nullptr, *cdf_i = nullptr, *tot = nullptr;
+    double *d_uf = nullptr, *d_ui = nullptr, *lf = nullptr, *bmaxf = nullptr;
+    pool.get((size_t)P, &q.J);
+    pool.get((size_t)P, &q.I);
+    if (given) {
+        pool.upload((const i64*)idx_fwd_host, (size_t)P, &J_in);
+        pool.upload((const i64*)idx_info_host, (size_t)P, &I_in);
+    } else {
+        pool.upload(u_fwd_host, (size_t)P, &d_uf);
+        pool.upload(u_info_host, (size_t)P, &d_ui);
+        pool.get((size_t)Nf, &cdf_f);
+        pool.get((size_t)Ni, &cdf_i);
+        pool.get((size_t)((Nmax + SM_CHUNK - 1) / SM_CHUNK), &tot);
+        if (w.d_mf) { pool.get((size_t)Nf, &lf); pool.get((size_t)nbf, &bmaxf); }
+    }
+    if (pool.status() != SMC_OK) return pool.status();
+    if (!given) {
+        if (w.d_mf) {
+            const TfGamma none{0.0, 0.0, 0.0, 0};
+            SMC_LAUNCH(k_tf_lwi, dim3(nbf), dim3(SMC_BLOCK), st, s.lwt, s.Xt, none, (const double*)w.d_mf, Nf, lf, bmaxf);
+            tf_cdf_of(st, lf, bmaxf, Nf, w.gmax + 1, tot, cdf_f);
+        } else {
+            sm_weights_cdf(f, island, s.t, s, tot, cdf_f);
+        }
+        tf_cdf_of(st, w.lwi, w.bmaxi, Ni, w.gmax + 2, tot, cdf_i);               // (the stream orders the two uses of tot)
+        q.cdf_f = cdf_f; q.cdf_i = cdf_i;
+    }
+    q.Xi = w.Xi; q.u_f = d_uf; q.u_i = d_ui; q.J_in = J_in; q.I_in = I_in; q.mf = w.d_mf; q.mi = w.d_mi;
+    q.items = w.items; q.Ni = Ni; q.P = P;
+    sm_with_kind(f->kind, [&](auto k) {
+        SMC_LAUNCH((k_tf_pairs<decltype(k)::value>), dim3((unsigned)((P + SMC_BLOCK - 1) / SMC_BLOCK)), dim3(SMC_BLOCK), st, s, q, psi);
+    });
+    return SMC_OK;
+}
 int smc_filter_two_filter(smc_filter* f, int island, smc_filter* info, int island_info, int64_t t, int method,
                           const smc_addfunc* phi, const double* loggamma3,
                           const double* modif_forward_host, const double* modif_info_host,
@@ -2488,12 +2561,12 @@ int smc_filter_two_filter(smc_filter* f, int island, smc_filter* info, int islan
                           int64_t* idx_fwd_out_host, int64_t* idx_info_out_host,
                           double* est_out_host, double* ess_out_host)
 {
-    if (f) { (void)hipSetDevice(f->ctx->device); flush_rows(f); }
+    sm_enter(f);
     SMC_REQUIRE(f && info && phi && loggamma3 && est_out_host, "null argument");
     SMC_REQUIRE(f->ctx == info->ctx, "the two filters must share a context");
     flush_rows(info);
-    int rc = sm_check_filter(__func__, f, island, est_out_host);
-    if (rc != SMC_OK) return rc;
+    const char* bad = sm_check_filter(f, island, est_out_host);
+    SMC_REQUIRE(!bad, bad);
     SMC_REQUIRE(info->kind != SMC_MODEL_MVLINGAUSS, "the information filter must be univariate");
     SMC_REQUIRE(!info->plan.sqmc(), "SQMC information filters are not supported");
     SMC_REQUIRE(info->a.hist == 1, "the information filter was created without a whole history (keep_history = 1)");
@@ -2518,106 +2591,44 @@ int smc_filter_two_filter(smc_filter* f, int island, smc_filter* info, int islan
     memcpy(psi.c, phi->c, sizeof psi.c);
     hipStream_t st = f->ctx->stream;
     SmPool pool(f->ctx);
-    const double* Xf = f_X(f->a, t) + (size_t)island * Nf;
-    const double* lwf = f_lw(f->a, t) + (size_t)island * Nf;
-    const double* Xi = f_X(info->a, ti) + (size_t)island_info * Ni;
-    const double* lwg = f_lw(info->a, ti) + (size_t)island_info * Ni;
-    const unsigned nbi = (unsigned)((Ni + SMC_BLOCK - 1) / SMC_BLOCK), nbf = (unsigned)((Nf + SMC_BLOCK - 1) / SMC_BLOCK);
+    const double* lwg = sm_lw(info, island_info, ti);
+    const unsigned nbi = (unsigned)((Ni + SMC_BLOCK - 1) / SMC_BLOCK);
     const i64 nitems = on ? P : Ni;
     const int nchunks = (int)((nitems + TF_CHUNK - 1) / TF_CHUNK);
-    double *lwi = nullptr, *bmaxi = nullptr, *gmax = nullptr, *out = nullptr, *items = nullptr, *cmax = nullptr, *cpart = nullptr;
-    double *d_mf = nullptr, *d_mi = nullptr;
-    rc = pool.get((size_t)Ni, &lwi);
-    if (rc == SMC_OK) rc = pool.get((size_t)nbi, &bmaxi);
-    if (rc == SMC_OK) rc = pool.get((size_t)3, &gmax);
-    if (rc == SMC_OK) rc = pool.get((size_t)OS_KMAX + 1, &out);
-    if (rc == SMC_OK) rc = pool.get((size_t)nitems * (K + 2), &items);
-    if (rc == SMC_OK) rc = pool.get((size_t)nchunks, &cmax);
-    if (rc == SMC_OK) rc = pool.get((size_t)nchunks * TF_PART, &cpart);
-    if (rc == SMC_OK && on) rc = pool.upload(modif_forward_host, (size_t)Nf, &d_mf);
-    if (rc == SMC_OK && on) rc = pool.upload(modif_info_host, (size_t)Ni, &d_mi);
+    TfWork w{};
+    w.Xi = sm_X(info, island_info, ti);
+    w.Ni = Ni;
+    double *out = nullptr, *cmax = nullptr, *cpart = nullptr;
+    pool.get((size_t)Ni, &w.lwi);
+    pool.get((size_t)nbi, &w.bmaxi);
+    pool.get((size_t)3, &w.gmax);
+    pool.get((size_t)OS_KMAX + 1, &out);
+    pool.get((size_t)nitems * (K + 2), &w.items);
+    pool.get((size_t)nchunks, &cmax);
+    pool.get((size_t)nchunks * TF_PART, &cpart);
+    if (on) { pool.upload(modif_forward_host, (size_t)Nf, &w.d_mf); pool.upload(modif_info_host, (size_t)Ni, &w.d_mi); }
+    int rc = pool.status();
     if (rc != SMC_OK) return rc;
     const TfGamma gam{loggamma3[0], loggamma3[1], loggamma3[2], 1};
-    SMC_LAUNCH(k_tf_lwi, dim3(nbi), dim3(SMC_BLOCK), st, lwg, Xi, gam, (const double*)d_mi, Ni, lwi, bmaxi);
+    SMC_LAUNCH(k_tf_lwi, dim3(nbi), dim3(SMC_BLOCK), st, lwg, w.Xi, gam, (const double*)w.d_mi, Ni, w.lwi, w.bmaxi);
     SmArgs s = sm_args(f, island, P, seed, nullptr);
     s.t = (u32)t;
-    s.Xt = Xf; s.lwt = lwf;
-    s.aux = f->a.aux ? f->a.aux + (t + 1) : nullptr;
-    i64 *J = nullptr, *I = nullptr;
-    if (!on) {
-        const int nslices = tf_slices(Ni, Nf);
-        double *loc = nullptr, *part = nullptr;
-        rc = pool.get((size_t)Nf, &loc);
-        if (rc == SMC_OK) rc = pool.get((size_t)nslices * Ni * 4, &part);
-        if (rc != SMC_OK) return rc;
-        int slot = 1;
-        switch (f->kind) {
-        case SMC_MODEL_LINGAUSS: os_launch_loc<SMC_MODEL_LINGAUSS>(st, s, loc); slot = sm_scale_slot<SMC_MODEL_LINGAUSS>(); break;
-        case SMC_MODEL_STOCHVOL: os_launch_loc<SMC_MODEL_STOCHVOL>(st, s, loc); slot = sm_scale_slot<SMC_MODEL_STOCHVOL>(); break;
-        case SMC_MODEL_GORDON: os_launch_loc<SMC_MODEL_GORDON>(st, s, loc); slot = sm_scale_slot<SMC_MODEL_GORDON>(); break;
-        case SMC_MODEL_THETALOGISTIC:
-            os_launch_loc<SMC_MODEL_THETALOGISTIC>(st, s, loc); slot = sm_scale_slot<SMC_MODEL_THETALOGISTIC>(); break;
-        default: os_launch_loc<SMC_MODEL_DISCRETECOX>(st, s, loc); slot = sm_scale_slot<SMC_MODEL_DISCRETECOX>(); break;
-        }
-        TfOn2 o{};
-        o.Xi = Xi; o.Xf = Xf; o.lwf = lwf; o.loc = loc; o.part = part; o.p = s.p; o.slot = slot; o.Ni = Ni; o.Nf = Nf;
-        const i64 ntile = (Nf + SMC_BLOCK - 1) / SMC_BLOCK;
-        o.per_slice = ((ntile + nslices - 1) / nslices) * SMC_BLOCK;
-        const int used = (int)((Nf + o.per_slice - 1) / o.per_slice);               // (no empty slice is launched or merged)
-        SMC_LAUNCH(k_tf_on2, dim3(nbi, (unsigned)used), dim3(SMC_BLOCK), st, o);
-        SMC_LAUNCH(k_tf_merge, dim3(nbi), dim3(SMC_BLOCK), st, psi, Xi, (const double*)lwi, (const double*)part, used, Ni, items);
-    } else {
-        TfPairs q{};
-        i64 *J_in = nullptr, *I_in = nullptr;
-        double *d_uf = nullptr, *d_ui = nullptr;
-        rc = pool.get((size_t)P, &J);
-        if (rc == SMC_OK) rc = pool.get((size_t)P, &I);
-        if (rc == SMC_OK && given) rc = pool.upload((const i64*)idx_fwd_host, (size_t)P, &J_in);
-        if (rc == SMC_OK && given) rc = pool.upload((const i64*)idx_info_host, (size_t)P, &I_in);
-        if (rc == SMC_OK && !given) rc = pool.upload(u_fwd_host, (size_t)P, &d_uf);
-        if (rc == SMC_OK && !given) rc = pool.upload(u_info_host, (size_t)P, &d_ui);
-        if (rc != SMC_OK) return rc;
-        if (!given) {
-            const i64 Nmax = Nf > Ni ? Nf : Ni;
-            u64 *cdf_f = nullptr, *cdf_i = nullptr, *tot = nullptr;
-            rc = pool.get((size_t)Nf, &cdf_f);
-            if (rc == SMC_OK) rc = pool.get((size_t)Ni, &cdf_i);
-            if (rc == SMC_OK) rc = pool.get((size_t)((Nmax + SM_CHUNK - 1) / SM_CHUNK), &tot);
-            if (rc != SMC_OK) return rc;
-            if (d_mf) {
-                double *lf = nullptr, *bmaxf = nullptr;
-                rc = pool.get((size_t)Nf, &lf);
-                if (rc == SMC_OK) rc = pool.get((size_t)nbf, &bmaxf);
-                if (rc != SMC_OK) return rc;
-                const TfGamma none{0.0, 0.0, 0.0, 0};
-                SMC_LAUNCH(k_tf_lwi, dim3(nbf), dim3(SMC_BLOCK), st, lwf, Xf, none, (const double*)d_mf, Nf, lf, bmaxf);
-                tf_cdf_of(st, lf, bmaxf, Nf, gmax + 1, tot, cdf_f);
-            } else {
-                sm_weights_cdf(f, island, t, s, tot, cdf_f);
-            }
-            tf_cdf_of(st, lwi, bmaxi, Ni, gmax + 2, tot, cdf_i);                     // (the stream orders the two uses of tot)
-            q.cdf_f = cdf_f; q.cdf_i = cdf_i;
-        }
-        q.Xi = Xi; q.u_f = d_uf; q.u_i = d_ui; q.J_in = J_in; q.I_in = I_in; q.mf = d_mf; q.mi = d_mi;
-        q.J = J; q.I = I; q.items = items; q.Ni = Ni; q.P = P;
-        switch (f->kind) {
-        case SMC_MODEL_LINGAUSS: tf_launch_pairs<SMC_MODEL_LINGAUSS>(st, s, q, psi); break;
-        case SMC_MODEL_STOCHVOL: tf_launch_pairs<SMC_MODEL_STOCHVOL>(st, s, q, psi); break;
-        case SMC_MODEL_GORDON: tf_launch_pairs<SMC_MODEL_GORDON>(st, s, q, psi); break;
-        case SMC_MODEL_THETALOGISTIC: tf_launch_pairs<SMC_MODEL_THETALOGISTIC>(st, s, q, psi); break;
-        default: tf_launch_pairs<SMC_MODEL_DISCRETECOX>(st, s, q, psi); break;
-        }
-    }
-    SMC_LAUNCH(k_tf_item_max, dim3((unsigned)nchunks), dim3(SMC_BLOCK), st, (const double*)items, K + 2, nitems, cmax);
-    SMC_LAUNCH(k_tf_max_final, dim3(1), dim3(SMC_BLOCK), st, (const double*)cmax, (i64)nchunks, gmax);
-    SMC_LAUNCH(k_tf_item_sums, dim3((unsigned)nchunks), dim3(SMC_BLOCK), st, (const double*)items, K + 2, nitems, K,
-               (const double*)gmax, cpart);
+    s.Xt = sm_X(f, island, t); s.lwt = sm_lw(f, island, t);
+    s.aux = sm_aux(f, t + 1);
+    TfPairs q{};
+    rc = on ? tf_items_pairs(f, island, pool, s, psi, w, idx_fwd_host, idx_info_host, u_fwd_host, u_info_host, q)
+            : tf_items_on2(f, pool, s, psi, w);
+    if (rc != SMC_OK) return rc;
+    SMC_LAUNCH(k_tf_item_max, dim3((unsigned)nchunks), dim3(SMC_BLOCK), st, (const double*)w.items, K + 2, nitems, cmax);
+    SMC_LAUNCH(k_tf_max_final, dim3(1), dim3(SMC_BLOCK), st, (const double*)cmax, (i64)nchunks, w.gmax);
+    SMC_LAUNCH(k_tf_item_sums, dim3((unsigned)nchunks), dim3(SMC_BLOCK), st, (const double*)w.items, K + 2, nitems, K,
+               (const double*)w.gmax, cpart);
     SMC_LAUNCH(k_tf_final, dim3(1), dim3(64), st, (const double*)cpart, nchunks, K, out);
     SMC_LAUNCH_CHECK();
     double res[OS_KMAX + 1];
     SMC_HIP_CHECK(hipMemcpyAsync(res, out, sizeof res, hipMemcpyDeviceToHost, st));
-    if (on && idx_fwd_out_host) SMC_HIP_CHECK(hipMemcpyAsync(idx_fwd_out_host, J, (size_t)P * 8, hipMemcpyDeviceToHost, st));
-    if (on && idx_info_out_host) SMC_HIP_CHECK(hipMemcpyAsync(idx_info_out_host, I, (size_t)P * 8, hipMemcpyDeviceToHost, st));
+    if (on && idx_fwd_out_host) SMC_HIP_CHECK(hipMemcpyAsync(idx_fwd_out_host, q.J, (size_t)P * 8, hipMemcpyDeviceToHost, st));
+    if (on && idx_info_out_host) SMC_HIP_CHECK(hipMemcpyAsync(idx_info_out_host, q.I, (size_t)P * 8, hipMemcpyDeviceToHost, st));
     SMC_HIP_CHECK(hipStreamSynchronize(st));
     for (int k = 0; k < K; ++k) est_out_host[k] = res[k];
     if (ess_out_host) *ess_out_host = res[OS_KMAX];

@@ -278,8 +278,3 @@ static void os_launch_on2(hipStream_t st, const OsOn2& o, int nslices, const OsP
     SMC_LAUNCH((k_os_on2<KP>), dim3(nblk, (unsigned)nslices), dim3(SMC_BLOCK), st, o);
     SMC_LAUNCH((k_os_on2_merge<KP>), dim3(nblk), dim3(SMC_BLOCK), st, psi, o.X, (const double*)o.part, nslices, o.N, Phi_out);
 }
-template <int KIND>
-static void os_launch_loc(hipStream_t st, const SmArgs& s, double* loc)
-{
-    SMC_LAUNCH((k_os_loc<KIND>), dim3((unsigned)((s.N + SMC_BLOCK - 1) / SMC_BLOCK)), dim3(SMC_BLOCK), st, s, loc);
-}

@@ -419,37 +419,33 @@ k_sm_paths(const FArgs av, int isl, i64 t_end, i64 M, const i64* idx, double* ou
 // ---------------------------------------------------------------------------
 // host side helpers of smc_filter_backward_sample
 // ---------------------------------------------------------------------------
-struct SmPool {                    // blocks handed back to the pool on every way out
+// Blocks handed back to the pool on every way out.  The status is sticky: after the first failure get and upload do
+// nothing and hand back null, so a caller acquires in plain statements and looks at status() once.
+struct SmPool {
     smc_ctx* ctx;
     std::vector<void*> blocks;
+    int rc = SMC_OK;
     explicit SmPool(smc_ctx* c) : ctx(c) {}
     ~SmPool() { for (void* b : blocks) (void)smc_free(ctx, b); }
-    template <class T> int get(size_t n, T** out)
+    int status() const { return rc; }                // the first failure's code
+    template <class T> void get(size_t n, T** out)     // (n == 0: one element)
     {
         void* p = nullptr;
-        const int rc = smc_malloc(ctx, (n ? n : 1) * sizeof(T), &p);
-        if (rc == SMC_OK) blocks.push_back(p);
+        if (rc == SMC_OK && (rc = smc_malloc(ctx, (n ? n : 1) * sizeof(T), &p)) == SMC_OK) blocks.push_back(p);
         *out = (T*)p;
-        return rc;
     }
-    template <class T> int upload(const T* host, size_t n, T** out)
+    template <class T> void upload(const T* host, size_t n, T** out)    // (null host: nothing uploaded, *out = null, no error)
     {
         *out = nullptr;
-        if (!host) return SMC_OK;
-        const int rc = get(n, out);
-        if (rc != SMC_OK) return rc;
+        if (host) get(n, out);
+        if (*out) rc = copy_in(host, n, out);
+    }
+    template <class T> int copy_in(const T* host, size_t n, T** out)
+    {
         SMC_HIP_CHECK(hipMemcpyAsync(*out, host, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
         return SMC_OK;
     }
 };
-template <int KIND>
-static void sm_launch_step(int method, hipStream_t st, const SmArgs& s)
-{
-    if (method == SMC_BACKWARD_ON2)
-        SMC_LAUNCH((k_sm_on2<KIND>), dim3((unsigned)s.M), dim3(SMC_BLOCK), st, s);
-    else
-        SMC_LAUNCH((k_sm_mcmc<KIND>), dim3((unsigned)((s.M + SMC_BLOCK - 1) / SMC_BLOCK)), dim3(SMC_BLOCK), st, s);
-}
 // Trials of the first launch.  SMC_REJECT_SOLO_TRIALS (measurements only, tools/ffbs_perf.py): a value >= max_trials
 // leaves the wave launch nothing but to pass the unresolved on.  The drawn indices do not depend on it.
 static i64 sm_reject_solo_trials()

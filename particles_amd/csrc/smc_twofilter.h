@@ -344,8 +344,3 @@ static void tf_cdf_of(hipStream_t st, const double* l, const double* bmax, i64 N
     SMC_LAUNCH(k_tf_cdf_totals, dim3(nch), dim3(SMC_BLOCK), st, l, (const double*)gmax, N, sm_shift(N), tot);
     SMC_LAUNCH(k_tf_cdf_scan, dim3(nch), dim3(SMC_BLOCK), st, l, (const double*)gmax, N, sm_shift(N), (const u64*)tot, cdf);
 }
-template <int KIND>
-static void tf_launch_pairs(hipStream_t st, const SmArgs& s, const TfPairs& q, const OsPsi& f)
-{
-    SMC_LAUNCH((k_tf_pairs<KIND>), dim3((unsigned)((q.P + SMC_BLOCK - 1) / SMC_BLOCK)), dim3(SMC_BLOCK), st, s, q, f);
-}

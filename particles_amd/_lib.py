@@ -398,29 +398,71 @@ class DeviceArray:
            "log": 8, "sqrt": 9, "cos": 10, "sin": 11, "abs": 12, "square": 13, "pow": 14,
            "min": 15, "max": 16, "arctan": 17}
 
+    @staticmethod
+    def _flat_stride(shape, size, out_shape, out_size):
+        """How k_elementwise walks an operand of ``shape`` inside a C-ordered result of ``out_shape``: 1 (element i),
+        0 (one value) or -m (element i mod m: the operand is the trailing block of the result, as a (d,) row is of
+        (N, d)).  A form with no such stride -- an (N, 1) column against (N, d) -- is refused."""
+        if size == out_size:
+            return 1                                    # (the same extents but for leading 1s)
+        if size == 1:
+            return 0
+        k = 0
+        while shape[k] == 1:
+            k += 1
+        if out_shape[len(out_shape) - (len(shape) - k):] == shape[k:]:
+            return -size
+        raise ValueError("operands could not be broadcast together on the device: %s is not the trailing block of the "
+                         "result %s (a column against (N, d) has no stride form)" % (shape, out_shape))
+
+    @staticmethod
+    def _broadcast(s, t):
+        """numpy's broadcast shape of two shapes (plain Python: this runs once per operator call)."""
+        if len(s) < len(t):
+            s, t = t, s
+        out = list(s)
+        off = len(s) - len(t)
+        for k, m in enumerate(t):
+            n = out[off + k]
+            if n == 1:
+                out[off + k] = m
+            elif m != 1 and m != n:
+                raise ValueError("operands could not be broadcast together with shapes %s %s" % (s, t))
+        return tuple(out)
+
     def _ew(self, op, other=None):
+        """One element-wise launch.  Shapes follow numpy's broadcasting rules, restricted to the forms the kernel has a
+        stride for (_flat_stride); a device operand that is not float64 is refused -- there is no conversion kernel."""
         if self.dtype != np.float64:
             raise TypeError("device arithmetic is defined for float64 arrays")
         b, sb, alpha, shape = None, 0, 0.0, self.shape
         a, sa = self, 1
         if other is not None:
-            if not isinstance(other, DeviceArray) and np.size(other) > 1:
-                other = DeviceArray.from_numpy(np.asarray(other, dtype=np.float64), context=self.ctx)
             if isinstance(other, DeviceArray):
-                if other.size == self.size:
-                    b, sb = other, 1
-                elif other.size == 1:
-                    b, sb = other, 0
-                elif self.size == 1:
-                    sa, b, sb, shape = 0, other, 1, other.shape
-                elif self.ndim == 2 and other.size == self.shape[1]:      # (N, d) with a (d,) row
-                    b, sb = other, -self.shape[1]
-                elif other.ndim == 2 and self.size == other.shape[1]:
-                    sa, b, sb, shape = -other.shape[1], other, 1, other.shape
-                else:
-                    raise ValueError("operands could not be broadcast together")
+                if other.dtype != np.float64:
+                    raise TypeError("device arithmetic is defined for float64 arrays")
+            elif type(other) is not float and type(other) is not int:
+                other = np.asarray(other, dtype=np.float64)         # (a host operand: checked on its numpy shape)
+                if other.ndim == 0:
+                    other = float(other)
+            if type(other) is float or type(other) is int:
+                alpha = float(other)
             else:
-                alpha = float(np.asarray(other).reshape(-1)[0])
+                if other.shape == shape:
+                    sb = 1
+                else:
+                    shape = self._broadcast(shape, other.shape)
+                    size = 1
+                    for s in shape:
+                        size *= s
+                    sa = self._flat_stride(self.shape, self.size, shape, size)
+                    sb = self._flat_stride(other.shape, other.size, shape, size)
+                if isinstance(other, DeviceArray):
+                    b = other
+                elif other.size == 1:
+                    alpha = float(other.reshape(-1)[0])
+                else:
+                    b = DeviceArray.from_numpy(other, context=self.ctx)
         out = DeviceArray(shape, np.float64, self.ctx)
         check(lib().smc_elementwise(self.ctx.h, self._EW[op], a.ptr, sa, b.ptr if b is not None else None,
                                     sb, alpha, out.size, out.ptr))
@@ -438,11 +480,12 @@ class DeviceArray:
     def __abs__(self): return self._ew("abs")
 
     def __pow__(self, e):
-        if np.ndim(e) == 0 and e == 2:
-            return self._ew("square")           # as numpy: x ** 2 is x * x
-        if np.ndim(e) == 0 and e == 0.5:
-            return self._ew("sqrt")
-        return self._ew("pow", e)
+        if not isinstance(e, DeviceArray) and np.ndim(e) == 0:
+            if e == 2:
+                return self._ew("square")       # as numpy: x ** 2 is x * x
+            if e == 0.5:
+                return self._ew("sqrt")
+        return self._ew("pow", e)               # (an array exponent, device or host, included)
 
     _UFUNCS = {"add": ("add", "add"), "subtract": ("sub", "rsub"), "multiply": ("mul", "mul"),
                "true_divide": ("div", "rdiv"), "divide": ("div", "rdiv"),
@@ -494,14 +537,37 @@ class DeviceArray:
 
     def __getitem__(self, idx):
         """``x[A]`` with a device or host int64 index array (core.py:332 Xp = X[A]);
-        ``x[..., i]`` / ``x[:, i]``: one column of an (N, d) array."""
-        if isinstance(idx, tuple) and len(idx) == 2 and isinstance(idx[1], (int, np.integer)) \
-                and (idx[0] is Ellipsis or idx[0] == slice(None)):
-            return self.column(idx[1])
-        A = idx if isinstance(idx, DeviceArray) else DeviceArray.from_numpy(
-            np.ascontiguousarray(idx, dtype=np.int64), context=self.ctx)
-        if A.dtype != np.int64:
-            raise TypeError("DeviceArray indexing takes an int64 index array")
+        ``x[..., i]`` / ``x[:, i]``: one column of an (N, d) array.
+
+        A host index follows numpy: a boolean mask over the rows selects, negative indices wrap, and an index array
+        that is not of integer type, or holds an index outside [-N, N), raises IndexError.  A device index array is
+        NOT checked -- that would put a reduction and a synchronisation into the ``X[A]`` of every step: its entries
+        must lie in [0, N)."""
+        if isinstance(idx, tuple):
+            if len(idx) == 2 and isinstance(idx[1], (int, np.integer)) \
+                    and (idx[0] is Ellipsis or (isinstance(idx[0], slice) and idx[0] == slice(None))):
+                return self.column(idx[1])
+            raise TypeError("DeviceArray indexing takes x[A] with an index array A, x[..., i] or x[:, i]")
+        if isinstance(idx, DeviceArray):
+            A = idx
+            if A.dtype != np.int64:
+                raise TypeError("DeviceArray indexing takes an int64 index array")
+        else:
+            n = self.shape[0]
+            ih = np.asarray(idx)
+            if ih.dtype == np.bool_:
+                if ih.shape != (n,):
+                    raise IndexError("boolean index did not match indexed array along axis 0; size of axis is %d "
+                                     "but the mask has shape %s" % (n, ih.shape))
+                ih = np.flatnonzero(ih)
+            elif ih.dtype.kind not in "iu":
+                raise IndexError("arrays used as indices must be of integer (or boolean) type")
+            ih = ih.astype(np.int64)
+            ih[ih < 0] += n
+            if ih.size and (ih.min() < 0 or ih.max() >= n):
+                bad = ih[(ih < 0) | (ih >= n)].reshape(-1)[0]
+                raise IndexError("index %d is out of bounds for axis 0 with size %d" % (bad - (n if bad < 0 else 0), n))
+            A = DeviceArray.from_numpy(ih, dtype=np.int64, context=self.ctx)
         d = self.size // self.shape[0]
         # (8-byte elements either way: an int64 array -- h_order[idx], core.py:344 -- is gathered
         # by the same kernel, which only copies words)
@@ -514,6 +580,8 @@ class DeviceArray:
 
     def __matmul__(self, M):
         """``X @ M`` for device rows ``X`` (N, d) and a small host matrix ``M`` (d, k)."""
+        if self.dtype != np.float64:
+            raise TypeError("device arithmetic is defined for float64 arrays")
         Mh = np.ascontiguousarray(M, dtype=np.float64)
         d = self.shape[-1] if self.ndim == 2 else 1
         if Mh.ndim != 2 or Mh.shape[0] != d:

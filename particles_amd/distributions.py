@@ -50,9 +50,19 @@ class LocScaleDist(ProbDist):
         self.scale = scale
 
 
+def _f64(v):
+    """The kernels read 8-byte words as doubles and there is no conversion kernel: an int64 device array is refused."""
+    if v.dtype != np.float64:
+        raise TypeError("device arithmetic is defined for float64 arrays")
+    return v
+
+
 def _strided(v, N):
     """(DeviceArray, element stride, is_device_input) for a scalar / (1,) / (N,) value."""
     if isinstance(v, DeviceArray):
+        _f64(v)
+        if v.size not in (1, N):
+            raise ValueError("operands could not be broadcast together with shape (%d,)" % N)
         return v, (0 if v.size == 1 else 1), True
     if isinstance(v, (float, int, np.floating)):           # (the common case: a scalar parameter)
         return DeviceArray.scalar(v), 0, False
@@ -84,8 +94,10 @@ class Normal(LocScaleDist):
             z = random.standard_normal(N)      # random.normal(loc, scale, N) draws exactly these
         zd = None
         if z is not None:
-            zd = z if isinstance(z, DeviceArray) else DeviceArray.from_numpy(
+            zd = _f64(z) if isinstance(z, DeviceArray) else DeviceArray.from_numpy(
                 np.asarray(z, dtype=np.float64).reshape(-1))
+            if zd.size != N:
+                raise ValueError("Normal.rvs: z has %d values, expected %d" % (zd.size, N))
         out = DeviceArray((N,))
         check(lib().smc_normal_rvs(out.ctx.h, loc.ptr, ls, sc.ptr, ss,
                                    zd.ptr if zd is not None else None,
@@ -210,6 +222,9 @@ class MvNormal(ProbDist):
 
     def _loc(self, N):
         if isinstance(self.loc, DeviceArray):
+            if _f64(self.loc).size not in (self.dim, N * self.dim):
+                raise ValueError("MvNormal: loc has %d values, expected %d or %d x %d"
+                                 % (self.loc.size, self.dim, N, self.dim))
             return self.loc, (1 if self.loc.size == self.dim else N), True
         a = np.asarray(self.loc, dtype=np.float64)
         if a.ndim == 0:
@@ -241,8 +256,10 @@ class MvNormal(ProbDist):
             z = random.standard_normal((N, self.dim))      # stats.norm.rvs(size=(N, d)) (:968)
         zd = None
         if z is not None:
-            zd = z if isinstance(z, DeviceArray) else DeviceArray.from_numpy(
+            zd = _f64(z) if isinstance(z, DeviceArray) else DeviceArray.from_numpy(
                 np.asarray(z, dtype=np.float64).reshape(N, self.dim))
+            if zd.size != N * self.dim:
+                raise ValueError("MvNormal.rvs: z has %d values, expected %d x %d" % (zd.size, N, self.dim))
         out = DeviceArray((N, self.dim))
         La, Lp = _lib.host_dbl(self.L)  # keep La alive across the call
         check(lib().smc_mvn_rvs(out.ctx.h, loc.ptr, rows, float(self.scale), Lp,
@@ -255,7 +272,7 @@ class MvNormal(ProbDist):
         """linear_transform(norm.ppf(u)) for u (N, du) (:970-981); du = dim only (the partly
         degenerate case du < dim of the reference is not built)."""
         ud, host = _lib.as_device(u)
-        N, du = ud.shape
+        N, du = _f64(ud).shape
         if du != self.dim:
             raise NotImplementedError("MvNormal.ppf: u must have dim = %d columns" % self.dim)
         z = DeviceArray((N, du), np.float64, ud.ctx)
@@ -275,6 +292,8 @@ class MvNormal(ProbDist):
             base = base.get() if isinstance(base, DeviceArray) else base
             return base - np.sum(np.log(sc), axis=-1)
         if isinstance(x, DeviceArray):
+            if _f64(x).size % self.dim:
+                raise ValueError("MvNormal: x has %d values, not a multiple of d = %d" % (x.size, self.dim))
             xd, xrows, dx = x, x.size // self.dim, True
         else:
             xa = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, self.dim))

@@ -161,6 +161,8 @@ class Weights:
         self.lw = lw
         if lw is not None:
             if isinstance(lw, DeviceArray):
+                if lw.dtype != np.float64:
+                    raise TypeError("device arithmetic is defined for float64 arrays")
                 d = lw
             else:
                 self.lw[np.isnan(self.lw)] = -np.inf        # :220, caller's array

@@ -150,6 +150,80 @@ struct smc_filter {
     const double* xstar = nullptr;
 };
 
+// ---- from a run-time word to a template argument.  Every launch below that chooses among instantiations of one kernel
+// goes through these: the word becomes a type (fn(std::integral_constant<..>{})), the kernel template is named once, and its
+// grid, block, stream and arguments are written once.  A combination that does not exist is left out with `if constexpr` in
+// the lambda, so it is never instantiated; a word outside the set calls nothing.
+// F_VAL(x): the value of such a type by its parameter's name (remove_reference: g++ gives decltype of a parameter that an
+// inner lambda captures by reference as T&)
+#define F_VAL(x) std::remove_reference_t<decltype(x)>::value
+template <class F>
+static void f_with_bool(bool b, F&& fn)
+{
+    if (b) fn(std::true_type{});
+    else fn(std::false_type{});
+}
+template <int... VS, class F>
+static void f_with_value(int v, F&& fn)
+{
+    (void)((v == VS ? (fn(std::integral_constant<int, VS>{}), true) : false) || ...);
+}
+// the one-workgroup kernels (k_filter_small, k_csmc_small, k_csmc_path): one wave up to N = 256
+template <class F>
+static void f_with_small_block(i64 N, F&& fn)
+{
+    f_with_value<64, SMC_BLOCK>(N <= 256 ? 64 : SMC_BLOCK, fn);
+}
+// k_f_spacing_onepass<tiles of draws per workgroup>: launch_spacings launches it, plan_step asks for its occupancy
+template <class F>
+static void f_with_onepass(int tpw, F&& fn)
+{
+    f_with_value<1, 2, 4, 8>(tpw, [&](auto v) { fn(k_f_spacing_onepass<F_VAL(v)>); });
+}
+
+// The univariate models of the fused filter are named here and nowhere else: the six kinds in f_with_kind, the Feynman-Kac
+// kinds each of them runs under in f_pair_ok.  smc_filter_create refuses what f_model_ok does not find, so the launches
+// (k_propagate, k_filter_small, k_sq_permute) meet existing pairs only.  No default, as in sm_with_kind.
+template <int KIND, int FK>
+constexpr bool f_pair_ok()
+{
+    return FK == SMC_FK_BOOTSTRAP || ((FK == SMC_FK_GUIDED || FK == SMC_FK_APF || FK == SMC_FK_APF_BOOT) &&
+                                      (KIND == SMC_MODEL_LINGAUSS || KIND == SMC_MODEL_STOCHVOL));
+}
+template <class F>
+static void f_with_kind(int kind, F&& fn)
+{
+    switch (kind) {
+    case SMC_MODEL_LINGAUSS: fn(std::integral_constant<int, SMC_MODEL_LINGAUSS>{}); break;
+    case SMC_MODEL_STOCHVOL: fn(std::integral_constant<int, SMC_MODEL_STOCHVOL>{}); break;
+    case SMC_MODEL_GORDON: fn(std::integral_constant<int, SMC_MODEL_GORDON>{}); break;
+    case SMC_MODEL_THETALOGISTIC: fn(std::integral_constant<int, SMC_MODEL_THETALOGISTIC>{}); break;
+    case SMC_MODEL_SVLEVERAGE: fn(std::integral_constant<int, SMC_MODEL_SVLEVERAGE>{}); break;
+    case SMC_MODEL_DISCRETECOX: fn(std::integral_constant<int, SMC_MODEL_DISCRETECOX>{}); break;
+    }
+}
+template <class F>
+static void f_with_model(int kind, int fk, F&& fn)
+{
+    f_with_kind(kind, [&](auto k) {
+        f_with_value<SMC_FK_BOOTSTRAP, SMC_FK_GUIDED, SMC_FK_APF, SMC_FK_APF_BOOT>(fk, [&](auto q) {
+            if constexpr (f_pair_ok<F_VAL(k), F_VAL(q)>()) fn(k, q);
+        });
+    });
+}
+static bool f_kind_ok(int kind)
+{
+    bool ok = false;
+    f_with_kind(kind, [&](auto) { ok = true; });
+    return ok;
+}
+static bool f_model_ok(int kind, int fk)
+{
+    bool ok = false;
+    f_with_model(kind, fk, [&](auto, auto) { ok = true; });
+    return ok;
+}
+
 // the uniforms of a multinomial step are drawn on the device (no replay tape: smc_filter_set_replay may set one later)
 static bool philox_multinomial(const FArgs& a) { return a.scheme == SMC_MULTINOMIAL && !a.ut; }
 
@@ -231,8 +305,8 @@ static int plan_step(const smc_ctx* ctx, const smc_model* model, const smc_filte
             (void)ctx;
 #else
             int per_cu = 0;                        // workgroups of this instantiation a CU holds at once
-            const void* fn = tpw == 1 ? (const void*)k_f_spacing_onepass<1> : tpw == 2 ? (const void*)k_f_spacing_onepass<2>
-                           : tpw == 4 ? (const void*)k_f_spacing_onepass<4> : (const void*)k_f_spacing_onepass<8>;
+            const void* fn = nullptr;
+            f_with_onepass(tpw, [&](auto kernel) { fn = (const void*)kernel; });
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, SMC_BLOCK, 0) != hipSuccess) per_cu = 0;
             (void)hipGetLastError();
             // (a margin of one workgroup per CU: the occupancy API is optimistic near register-file edges)
@@ -279,68 +353,37 @@ static void launch_propagate(smc_filter* f)
 {
     hipStream_t st = f->ctx->stream;
     const dim3 grid(f->a.nparts, f->a.n_islands);
-    const bool two_level = f->plan.two_level;
-    const int ragged = f->plan.ragged;
     if (f->kind == SMC_MODEL_MVLINGAUSS) {
-#define MV_CASE(FKV, DPV, COLLV)                                                            \
-    if (f->fk == FKV && f->a.dp == DPV && f->plan.mv_collapsed == COLLV) {                  \
-        if (f->a.dx == DPV && f->a.mv_diag)                                                 \
-            SMC_LAUNCH((k_propagate_mv<FKV, DPV, true, COLLV, true>), grid, dim3(SMC_BLOCK), st,  \
-                       f->a, f->a.mvc);                                                     \
-        else if (f->a.mv_diag)                                                              \
-            SMC_LAUNCH((k_propagate_mv<FKV, DPV, false, COLLV, true>), grid, dim3(SMC_BLOCK), st, \
-                       f->a, f->a.mvc);                                                     \
-        else if (f->a.dx == DPV)                                                            \
-            SMC_LAUNCH((k_propagate_mv<FKV, DPV, true, COLLV>), grid, dim3(SMC_BLOCK), st,  \
-                       f->a, f->a.mvc);                                                     \
-        else                                                                                \
-            SMC_LAUNCH((k_propagate_mv<FKV, DPV, false, COLLV>), grid, dim3(SMC_BLOCK), st, \
-                       f->a, f->a.mvc);                                                     \
-        return;                                                                             \
-    }
-        MV_CASE(SMC_FK_BOOTSTRAP, 16, false) MV_CASE(SMC_FK_BOOTSTRAP, 32, false)
-        MV_CASE(SMC_FK_GUIDED, 16, false) MV_CASE(SMC_FK_GUIDED, 32, false)
-        MV_CASE(SMC_FK_GUIDED, 16, true) MV_CASE(SMC_FK_GUIDED, 32, true)
-        MV_CASE(SMC_FK_APF, 16, false) MV_CASE(SMC_FK_APF, 32, false)
-#undef MV_CASE
+        // fk, dp, dx == dp, the collapsed proposal (guided only), diagonal covariances
+        f_with_value<SMC_FK_BOOTSTRAP, SMC_FK_GUIDED, SMC_FK_APF>(f->fk, [&](auto q) {
+            f_with_value<16, 32>(f->a.dp, [&](auto dp) {
+                f_with_bool(f->a.dx == f->a.dp, [&](auto dfull) {
+                    f_with_bool(f->plan.mv_collapsed, [&](auto coll) {
+                        f_with_bool(f->a.mv_diag != 0, [&](auto dg) {
+                            constexpr int FK = F_VAL(q), DP = F_VAL(dp);
+                            constexpr bool DFULL = F_VAL(dfull), COLL = F_VAL(coll), DG = F_VAL(dg);
+                            if constexpr (!COLL || FK == SMC_FK_GUIDED)
+                                SMC_LAUNCH((k_propagate_mv<FK, DP, DFULL, COLL, DG>), grid, dim3(SMC_BLOCK), st, f->a, f->a.mvc);
+                        });
+                    });
+                });
+            });
+        });
         return;
     }
-// (k_propagate's leading arguments: the fields its first loads are addressed with, preloaded into SGPRs)
-#define P_LEAD f->a.A, f->a.info, f->a.params, f->a.hcnt, f->a.N, f->a.ntiles | (f->a.xcd_chunks ? 1 << 30 : 0)
-#define P_CASE(KINDV, FKV)                                                                    \
-    if (f->kind == KINDV && f->fk == FKV) {                                                   \
-        if (two_level && ragged == 1 && f->a.par >= 0)                                        \
-            SMC_LAUNCH((k_propagate<KINDV, FKV, F_OPT, true, false, 1>), grid, dim3(SMC_BLOCK), st, P_LEAD, f->a);  \
-        else if (two_level && ragged == 1)                                                    \
-            SMC_LAUNCH((k_propagate<KINDV, FKV, F_OPT, false, false, 1>), grid, dim3(SMC_BLOCK), st, P_LEAD, f->a); \
-        else if (two_level && ragged == 2 && f->a.par >= 0)                                   \
-            SMC_LAUNCH((k_propagate<KINDV, FKV, F_OPT, true, false, 2>), grid, dim3(SMC_BLOCK), st, P_LEAD, f->a);  \
-        else if (two_level && ragged == 2)                                                    \
-            SMC_LAUNCH((k_propagate<KINDV, FKV, F_OPT, false, false, 2>), grid, dim3(SMC_BLOCK), st, P_LEAD, f->a); \
-        else if (two_level && f->a.par >= 0)                                                  \
-            SMC_LAUNCH((k_propagate<KINDV, FKV, F_OPT, true, false>), grid, dim3(SMC_BLOCK), st, P_LEAD, f->a);  \
-        else if (two_level)                                                                   \
-            SMC_LAUNCH((k_propagate<KINDV, FKV, F_OPT, false, false>), grid, dim3(SMC_BLOCK), st, P_LEAD, f->a); \
-        else if (f->a.par >= 0)                                                               \
-            SMC_LAUNCH((k_propagate<KINDV, FKV, F_OPT, true>), grid, dim3(SMC_BLOCK), st, P_LEAD, f->a);  \
-        else                                                                                  \
-            SMC_LAUNCH((k_propagate<KINDV, FKV, F_OPT, false>), grid, dim3(SMC_BLOCK), st, P_LEAD, f->a); \
-        return;                                                                               \
-    }
-    P_CASE(SMC_MODEL_LINGAUSS, SMC_FK_BOOTSTRAP)
-    P_CASE(SMC_MODEL_LINGAUSS, SMC_FK_GUIDED)
-    P_CASE(SMC_MODEL_STOCHVOL, SMC_FK_BOOTSTRAP)
-    P_CASE(SMC_MODEL_STOCHVOL, SMC_FK_GUIDED)
-    P_CASE(SMC_MODEL_STOCHVOL, SMC_FK_APF)              // (tail-free two-level launches only: create checks)
-    P_CASE(SMC_MODEL_LINGAUSS, SMC_FK_APF)
-    P_CASE(SMC_MODEL_STOCHVOL, SMC_FK_APF_BOOT)
-    P_CASE(SMC_MODEL_LINGAUSS, SMC_FK_APF_BOOT)
-    P_CASE(SMC_MODEL_GORDON, SMC_FK_BOOTSTRAP)
-    P_CASE(SMC_MODEL_THETALOGISTIC, SMC_FK_BOOTSTRAP)
-    P_CASE(SMC_MODEL_SVLEVERAGE, SMC_FK_BOOTSTRAP)
-    P_CASE(SMC_MODEL_DISCRETECOX, SMC_FK_BOOTSTRAP)
-#undef P_CASE
-#undef P_LEAD
+    // the record's shape: -1 the flat step (k_propagate's tail), else tail-free with the plan's RAGGED
+    const int shape = f->plan.two_level ? f->plan.ragged : -1;
+    f_with_model(f->kind, f->fk, [&](auto k, auto q) {      // (APF: tail-free two-level launches only: create checks)
+        f_with_bool(f->a.par >= 0, [&](auto spec) {
+            f_with_value<-1, 0, 1, 2>(shape, [&](auto sh) {
+                constexpr int SH = F_VAL(sh);
+                // (the leading arguments: the fields the kernel's first loads are addressed with, preloaded into SGPRs)
+                SMC_LAUNCH((k_propagate<F_VAL(k), F_VAL(q), F_OPT, F_VAL(spec), (SH < 0), (SH < 0 ? 0 : SH)>), grid,
+                           dim3(SMC_BLOCK), st, f->a.A, f->a.info, f->a.params, f->a.hcnt, f->a.N,
+                           f->a.ntiles | (f->a.xcd_chunks ? 1 << 30 : 0), f->a);
+            });
+        });
+    });
 }
 
 // uniform_spacings for the Philox draws of a multinomial step, in the plan's form; merge: the island's reduction is
@@ -353,12 +396,7 @@ static void launch_spacings(smc_filter* f, hipStream_t st, bool merge)
     case SP_ONEPASS:
     case SP_ONEPASS_MERGED: {          // decoupled look-back: every workgroup resident
         const dim3 gw(a.sp_nwg + (merge ? 1 : 0), a.n_islands);
-        switch (a.sp_tpw) {
-        case 1: SMC_LAUNCH(k_f_spacing_onepass<1>, gw, dim3(SMC_BLOCK), st, a); break;
-        case 2: SMC_LAUNCH(k_f_spacing_onepass<2>, gw, dim3(SMC_BLOCK), st, a); break;
-        case 4: SMC_LAUNCH(k_f_spacing_onepass<4>, gw, dim3(SMC_BLOCK), st, a); break;
-        default: SMC_LAUNCH(k_f_spacing_onepass<8>, gw, dim3(SMC_BLOCK), st, a); break;
-        }
+        f_with_onepass(a.sp_tpw, [&](auto kernel) { SMC_LAUNCH(kernel, gw, dim3(SMC_BLOCK), st, a); });
         break;
     }
     case SP_THREE_PASS:                // two passes over the same draws (tile sums, their prefixes, the uniforms written once)
@@ -413,16 +451,12 @@ static void resample_sqmc(smc_filter* f, hipStream_t st, i64 t, bool t_known)
         if (a.n_islands == 1) { perm = v0; skeys = k0; }
         else (void)hipMemcpyAsync(f->sq_perm + (i64)i * a.N, v0, (size_t)a.N * 8, hipMemcpyDeviceToDevice, st);
     }
-#define SQ_CASE(KINDV)                                                                                           \
-    if (f->kind == KINDV) {                                                                                      \
-        if (recompute) SMC_LAUNCH((k_sq_permute<KINDV, true>), grid, dim3(SMC_BLOCK), st, f->a, perm, skeys, f->sq_z, \
-                                  f->sq_seed, f->sq_ctr0);                                                       \
-        else SMC_LAUNCH((k_sq_permute<KINDV, false>), grid, dim3(SMC_BLOCK), st, f->a, perm, skeys, f->sq_z,      \
-                        f->sq_seed, f->sq_ctr0);                                                                 \
-    }
-    SQ_CASE(SMC_MODEL_LINGAUSS) SQ_CASE(SMC_MODEL_STOCHVOL) SQ_CASE(SMC_MODEL_GORDON)
-    SQ_CASE(SMC_MODEL_THETALOGISTIC) SQ_CASE(SMC_MODEL_SVLEVERAGE) SQ_CASE(SMC_MODEL_DISCRETECOX)
-#undef SQ_CASE
+    f_with_kind(f->kind, [&](auto k) {
+        f_with_bool(recompute, [&](auto rc) {
+            SMC_LAUNCH((k_sq_permute<F_VAL(k), F_VAL(rc)>), grid, dim3(SMC_BLOCK), st, f->a, perm, skeys,
+                       f->sq_z, f->sq_seed, f->sq_ctr0);
+        });
+    });
     launch_reduce2(f, st);
     f->a.sq_perm = perm;                     // (A = h_order[sorted position]: composed where the ancestors are stored)
     SMC_LAUNCH((k_ancestors2<true, true, true, false, true>), grid, dim3(SMC_BLOCK), st, f->a);
@@ -453,8 +487,8 @@ static void resample_strict(smc_filter* f, hipStream_t st, bool t_known)
         break;
     case STRICT_TWO_LEVEL:
         // the same doubles in two launches, S never written (smc_filter_strict.h)
-        if (f->plan.reduce != REDUCE_NONE) SMC_LAUNCH(k_strict_classify<true>, gt, dim3(SMC_BLOCK), st, f->a, q);
-        else SMC_LAUNCH(k_strict_classify<false>, gt, dim3(SMC_BLOCK), st, f->a, q);
+        f_with_bool(f->plan.reduce != REDUCE_NONE,
+                    [&](auto mid) { SMC_LAUNCH(k_strict_classify<F_VAL(mid)>, gt, dim3(SMC_BLOCK), st, f->a, q); });
         SMC_LAUNCH(k_strict_search, gt, dim3(SMC_BLOCK), st, f->a, q);
         break;
     case STRICT_ARRAY: {
@@ -479,40 +513,40 @@ static void resample_two_level(smc_filter* f, hipStream_t st, bool t_known)
     if (f->a.scheme == SMC_MULTINOMIAL) {
         // searches over the sorted uniforms: the spacings just drawn (k_ancestors2 finds its window through the
         // tile prefixes) or the tape's
-        if (!f->a.ut) SMC_LAUNCH((k_ancestors2<true, true, true, true>), grid, dim3(SMC_BLOCK), st, f->a);
-        else SMC_LAUNCH((k_ancestors2<true, true>), grid, dim3(SMC_BLOCK), st, f->a);
+        f_with_bool(!f->a.ut, [&](auto regen) {
+            SMC_LAUNCH((k_ancestors2<true, true, true, F_VAL(regen)>), grid, dim3(SMC_BLOCK), st, f->a);
+        });
         return;
     }
-    // closed-form counts: one instantiation per scheme (see k_ancestors2's SCH)
+    // closed-form counts: one instantiation per scheme (see k_ancestors2's SCH); a launch of its own has reduced the
+    // island (MID), or the resampling workgroups do: one tile each, or F_WIDE_TPW tiles (k_ancestors2w)
+    const bool sys = f->a.scheme == SMC_SYSTEMATIC, p2 = f->a.log2N >= 0, mid = f->plan.reduce != REDUCE_NONE;
+    const bool wide = !mid && f->plan.resampler == RS_WIDE;
+    // k_ancestors2w's grid.  N = 2^k: the partials reduced by the workgroup's first 4 waves only; any N, systematic: the
+    // runs of tiles f_tile_xcd gives the XCDs, two tiles per workgroup
+    const int per_run = (f->a.ntiles + 7) / 8;
+    const dim3 gridw(p2 ? f->a.ntiles / F_WIDE_TPW : f->a.xcd_chunks ? 8 * ((per_run + 1) / 2) : (f->a.ntiles + 1) / 2,
+                     f->a.n_islands);
+    f_with_bool(sys, [&](auto s) {
+        f_with_bool(p2, [&](auto p) {
+            constexpr int SCH = F_VAL(s) ? SMC_SYSTEMATIC_ : SMC_STRATIFIED_;
+            constexpr bool POW2 = F_VAL(p);
 #ifdef SMC_NO_SCHEME_SPLIT                         /* (A/B builds: tools/build_ablations.sh) */
-#define A2_CASE(MIDV, POW2V, SCHV) SMC_LAUNCH((k_ancestors2<MIDV, false, POW2V>), grid, dim3(SMC_BLOCK), st, f->a)
+            constexpr int SCH_A2 = 0;
 #else
-#define A2_CASE(MIDV, POW2V, SCHV) SMC_LAUNCH((k_ancestors2<MIDV, false, POW2V, false, false, SCHV>), grid, dim3(SMC_BLOCK), st, f->a)
+            constexpr int SCH_A2 = SCH;
 #endif
-    const bool sys = f->a.scheme == SMC_SYSTEMATIC, p2 = f->a.log2N >= 0;
-    if (f->plan.reduce != REDUCE_NONE) {
-        if (p2) { if (sys) A2_CASE(true, true, SMC_SYSTEMATIC_); else A2_CASE(true, true, SMC_STRATIFIED_); }
-        else { if (sys) A2_CASE(true, false, SMC_SYSTEMATIC_); else A2_CASE(true, false, SMC_STRATIFIED_); }
-    } else if (f->plan.resampler == RS_WIDE) {
-        // (leading arguments: the fields the kernel's first loads are addressed with, preloaded into SGPRs)
-#define W_LEAD f->a.info2, f->a.pm, f->a.ps, f->a.pss, f->a.cq, f->a.N, f->a.ntiles | (f->a.xcd_chunks ? 1 << 30 : 0)
-        if (!p2) {
-            // any N, systematic: the runs of tiles f_tile_xcd gives the XCDs, two tiles per workgroup
-            const int per_run = (f->a.ntiles + 7) / 8;
-            const dim3 gridw(f->a.xcd_chunks ? 8 * ((per_run + 1) / 2) : (f->a.ntiles + 1) / 2, f->a.n_islands);
-            SMC_LAUNCH((k_ancestors2w<F_WIDE_TPW, SMC_SYSTEMATIC_, false>), gridw, dim3(SMC_BLOCK * 2), st, W_LEAD, f->a);
-        } else {
-            // N = 2^k: the partials reduced by the workgroup's first 4 waves only
-            const dim3 gridw(f->a.ntiles / F_WIDE_TPW, f->a.n_islands);
-            if (sys) SMC_LAUNCH((k_ancestors2w<F_WIDE_TPW, SMC_SYSTEMATIC_>), gridw, dim3(SMC_BLOCK * 2), st, W_LEAD, f->a);
-            else SMC_LAUNCH((k_ancestors2w<F_WIDE_TPW, SMC_STRATIFIED_>), gridw, dim3(SMC_BLOCK * 2), st, W_LEAD, f->a);
-        }
-#undef W_LEAD
-    } else {
-        if (p2) { if (sys) A2_CASE(false, true, SMC_SYSTEMATIC_); else A2_CASE(false, true, SMC_STRATIFIED_); }
-        else { if (sys) A2_CASE(false, false, SMC_SYSTEMATIC_); else A2_CASE(false, false, SMC_STRATIFIED_); }
-    }
-#undef A2_CASE
+            if (!wide) {
+                f_with_bool(mid, [&](auto m) {
+                    SMC_LAUNCH((k_ancestors2<F_VAL(m), false, POW2, false, false, SCH_A2>), grid, dim3(SMC_BLOCK), st, f->a);
+                });
+            } else if constexpr (POW2 || SCH == SMC_SYSTEMATIC_) {
+                // (leading arguments: the fields the kernel's first loads are addressed with, preloaded into SGPRs)
+                SMC_LAUNCH((k_ancestors2w<F_WIDE_TPW, SCH, POW2>), gridw, dim3(SMC_BLOCK * 2), st, f->a.info2, f->a.pm, f->a.ps,
+                           f->a.pss, f->a.cq, f->a.N, f->a.ntiles | (f->a.xcd_chunks ? 1 << 30 : 0), f->a);
+            }
+        });
+    });
 }
 
 // sq_flat: SQMC of a multivariate filter, or of a univariate one of fewer than two tiles (smc_filter_sqmc.h):
@@ -561,18 +595,19 @@ static void resample_flat(smc_filter* f, hipStream_t st, i64 t)
     if (f->kind == SMC_MODEL_MVLINGAUSS && f->fk == SMC_FK_APF) {
         // auxiliary weights of step t (core.py:307-313) before its resampling: smc_filter_mv.h
         const dim3 gp(f->a.nparts, f->a.n_islands);
-        if (f->a.dp == 16 && f->a.dx == 16) SMC_LAUNCH((k_mv_aux<16, true>), gp, dim3(SMC_BLOCK), st, f->a, f->a.mvc);
-        else if (f->a.dp == 16) SMC_LAUNCH((k_mv_aux<16, false>), gp, dim3(SMC_BLOCK), st, f->a, f->a.mvc);
-        else if (f->a.dx == 32) SMC_LAUNCH((k_mv_aux<32, true>), gp, dim3(SMC_BLOCK), st, f->a, f->a.mvc);
-        else SMC_LAUNCH((k_mv_aux<32, false>), gp, dim3(SMC_BLOCK), st, f->a, f->a.mvc);
+        auto go = [&](auto kernel) { SMC_LAUNCH(kernel, gp, dim3(SMC_BLOCK), st, f->a, f->a.mvc); };
+        f_with_value<16, 32>(f->a.dp, [&](auto dp) {
+            f_with_bool(f->a.dx == f->a.dp, [&](auto dfull) { go(k_mv_aux<F_VAL(dp), F_VAL(dfull)>); });
+        });
         SMC_LAUNCH(k_mv_aux_restate, dim3(f->a.n_islands), dim3(SMC_BLOCK), st, f->a);
     }
     const bool fused = f->plan.resampler == RS_FUSED;
     if (!fused) SMC_LAUNCH(k_prepare, grid, dim3(SMC_BLOCK), st, f->a);
     if (draws_spacings(f)) launch_spacings(f, st, false);
-    if (fused && f->a.par >= 0) SMC_LAUNCH((k_ancestors<true, true>), grid, dim3(SMC_BLOCK), st, f->a);
-    else if (fused) SMC_LAUNCH((k_ancestors<true, false>), grid, dim3(SMC_BLOCK), st, f->a);
-    else SMC_LAUNCH((k_ancestors<false, false>), grid, dim3(SMC_BLOCK), st, f->a);
+    // 0: behind k_prepare; 1: fused; 2: fused and SPEC (the slot parity is known) -- SPEC exists with the fused form only
+    f_with_value<0, 1, 2>(!fused ? 0 : f->a.par < 0 ? 1 : 2, [&](auto v) {
+        SMC_LAUNCH((k_ancestors<(F_VAL(v) >= 1), (F_VAL(v) == 2)>), grid, dim3(SMC_BLOCK), st, f->a);
+    });
     if (f->plan.sq_flat && t > 0)                  // A <- h_order[A] (core.py:344)
         for (int i = 0; i < f->a.n_islands; ++i)
             SMC_LAUNCH(k_sqmv_compose, dim3((unsigned)((f->a.N + SMC_BLOCK - 1) / SMC_BLOCK)), dim3(SMC_BLOCK), st, f->a, i,
@@ -853,19 +888,16 @@ static int fill_filter(smc_filter* f, const SlabLayout& L, const smc_model* mode
 }
 
 // The univariate kinds SmTrans evaluates the transition density of -- what backward sampling, on-line and two-filter
-// smoothing and conditional SMC take -- are named here and nowhere else: fn(std::integral_constant<int, kind>{}) is the one
-// switch from a kind to a template argument of their launches.  No default: another kind launches nothing, and every caller
-// has passed sm_kind_ok.  The lambdas hold launches only (SMC_REQUIRE, SMC_HIP_CHECK return from the function they stand in).
+// smoothing and conditional SMC take: the fused filter's kinds (f_with_kind) without SVLEVERAGE (its transition
+// reads y_{t-1}).  fn(std::integral_constant<int, kind>{}) is the one switch from a kind to a template argument of their
+// launches; another kind launches nothing, and every caller has passed sm_kind_ok.  The lambdas hold launches only
+// (SMC_REQUIRE, SMC_HIP_CHECK return from the function they stand in).
 template <class F>
 static void sm_with_kind(int kind, F&& fn)
 {
-    switch (kind) {
-    case SMC_MODEL_LINGAUSS: fn(std::integral_constant<int, SMC_MODEL_LINGAUSS>{}); break;
-    case SMC_MODEL_STOCHVOL: fn(std::integral_constant<int, SMC_MODEL_STOCHVOL>{}); break;
-    case SMC_MODEL_GORDON: fn(std::integral_constant<int, SMC_MODEL_GORDON>{}); break;
-    case SMC_MODEL_THETALOGISTIC: fn(std::integral_constant<int, SMC_MODEL_THETALOGISTIC>{}); break;
-    case SMC_MODEL_DISCRETECOX: fn(std::integral_constant<int, SMC_MODEL_DISCRETECOX>{}); break;
-    }
+    f_with_kind(kind, [&](auto k) {
+        if constexpr (F_VAL(k) != SMC_MODEL_SVLEVERAGE) fn(k);
+    });
 }
 static bool sm_kind_ok(int kind)
 {
@@ -891,15 +923,9 @@ int smc_filter_create(smc_ctx* ctx, const smc_model* model, const smc_filter_opt
         return SMC_ERR_SCHEME;
     }
     const bool mv = model->kind == SMC_MODEL_MVLINGAUSS;
-    SMC_REQUIRE(model->kind == SMC_MODEL_LINGAUSS || model->kind == SMC_MODEL_STOCHVOL || mv ||
-                    model->kind == SMC_MODEL_GORDON || model->kind == SMC_MODEL_THETALOGISTIC ||
-                    model->kind == SMC_MODEL_SVLEVERAGE || model->kind == SMC_MODEL_DISCRETECOX,
-                "fused filter: unknown model kind");
-    SMC_REQUIRE(model->fk == SMC_FK_BOOTSTRAP ||
-                    (model->fk == SMC_FK_GUIDED &&
-                     (model->kind == SMC_MODEL_LINGAUSS || model->kind == SMC_MODEL_STOCHVOL || mv)) ||
-                    (model->fk == SMC_FK_APF && (model->kind == SMC_MODEL_STOCHVOL || model->kind == SMC_MODEL_LINGAUSS || mv)) ||
-                    (model->fk == SMC_FK_APF_BOOT && (model->kind == SMC_MODEL_STOCHVOL || model->kind == SMC_MODEL_LINGAUSS)),
+    SMC_REQUIRE(mv || f_kind_ok(model->kind), "fused filter: unknown model kind");
+    SMC_REQUIRE(mv ? (model->fk == SMC_FK_BOOTSTRAP || model->fk == SMC_FK_GUIDED || model->fk == SMC_FK_APF)
+                   : f_model_ok(model->kind, model->fk),
                 "guided filter: LINGAUSS, STOCHVOL, MVLINGAUSS; auxiliary filter: STOCHVOL, LINGAUSS, MVLINGAUSS; "
                 "auxiliary bootstrap filter: STOCHVOL, LINGAUSS");
     {
@@ -1214,28 +1240,11 @@ static void launch_small(smc_filter* f, int nsteps)
     hipStream_t st = f->ctx->stream;
     const dim3 grid(1, f->a.n_islands);
     f->a.par = -1;
-#define S_CASE(KINDV, FKV)                                                                       \
-    if (f->kind == KINDV && f->fk == FKV) {                                                      \
-        if (f->a.N <= 256)                                                                       \
-            SMC_LAUNCH((k_filter_small<KINDV, FKV, 64>), grid, dim3(64), st, f->a, nsteps);      \
-        else                                                                                     \
-            SMC_LAUNCH((k_filter_small<KINDV, FKV, SMC_BLOCK>), grid, dim3(SMC_BLOCK), st, f->a, \
-                       nsteps);                                                                  \
-        return;                                                                                  \
-    }
-    S_CASE(SMC_MODEL_LINGAUSS, SMC_FK_BOOTSTRAP)
-    S_CASE(SMC_MODEL_LINGAUSS, SMC_FK_GUIDED)
-    S_CASE(SMC_MODEL_STOCHVOL, SMC_FK_BOOTSTRAP)
-    S_CASE(SMC_MODEL_STOCHVOL, SMC_FK_GUIDED)
-    S_CASE(SMC_MODEL_STOCHVOL, SMC_FK_APF)
-    S_CASE(SMC_MODEL_LINGAUSS, SMC_FK_APF)
-    S_CASE(SMC_MODEL_STOCHVOL, SMC_FK_APF_BOOT)
-    S_CASE(SMC_MODEL_LINGAUSS, SMC_FK_APF_BOOT)
-    S_CASE(SMC_MODEL_GORDON, SMC_FK_BOOTSTRAP)
-    S_CASE(SMC_MODEL_THETALOGISTIC, SMC_FK_BOOTSTRAP)
-    S_CASE(SMC_MODEL_SVLEVERAGE, SMC_FK_BOOTSTRAP)
-    S_CASE(SMC_MODEL_DISCRETECOX, SMC_FK_BOOTSTRAP)
-#undef S_CASE
+    f_with_model(f->kind, f->fk, [&](auto k, auto q) {
+        f_with_small_block(f->a.N, [&](auto bs) {
+            SMC_LAUNCH((k_filter_small<F_VAL(k), F_VAL(q), F_VAL(bs)>), grid, dim3(F_VAL(bs)), st, f->a, nsteps);
+        });
+    });
 }
 
 // Conditional SMC (smc_csmc.h): particle 0 of every island follows xstar (n_islands, T), a device buffer the caller owns.
@@ -1270,9 +1279,9 @@ static void launch_csmc(smc_filter* f, int nsteps)
     const dim3 grid(1, f->a.n_islands);
     f->a.par = -1;
     sm_with_kind(f->kind, [&](auto k) {
-        constexpr int KIND = decltype(k)::value;
-        if (f->a.N <= 256) SMC_LAUNCH((k_csmc_small<KIND, 64>), grid, dim3(64), st, f->a, nsteps, f->xstar);
-        else SMC_LAUNCH((k_csmc_small<KIND, SMC_BLOCK>), grid, dim3(SMC_BLOCK), st, f->a, nsteps, f->xstar);
+        f_with_small_block(f->a.N, [&](auto bs) {
+            SMC_LAUNCH((k_csmc_small<F_VAL(k), F_VAL(bs)>), grid, dim3(F_VAL(bs)), st, f->a, nsteps, f->xstar);
+        });
     });
 }
 
@@ -2161,9 +2170,9 @@ static int sm_launch_loc(smc_filter* f, const SmArgs& s, double* loc)
 {
     int slot = 1;
     sm_with_kind(f->kind, [&](auto k) {
-        SMC_LAUNCH((k_os_loc<decltype(k)::value>), dim3((unsigned)((s.N + SMC_BLOCK - 1) / SMC_BLOCK)), dim3(SMC_BLOCK),
+        SMC_LAUNCH((k_os_loc<F_VAL(k)>), dim3((unsigned)((s.N + SMC_BLOCK - 1) / SMC_BLOCK)), dim3(SMC_BLOCK),
                    f->ctx->stream, s, loc);
-        slot = sm_scale_slot<decltype(k)::value>();
+        slot = sm_scale_slot<F_VAL(k)>();
     });
     return slot;
 }
@@ -2212,8 +2221,8 @@ int smc_filter_backward_sample(smc_filter* f, int island, int method, int64_t M,
         s.u = d_u ? d_u + (size_t)b * per_step : nullptr;
         s.u_acc = d_uacc ? d_uacc + (size_t)b * per_step : nullptr;
         sm_with_kind(f->kind, [&](auto k) {
-            if (mcmc) SMC_LAUNCH((k_sm_mcmc<decltype(k)::value>), dim3((unsigned)((M + SMC_BLOCK - 1) / SMC_BLOCK)), dim3(SMC_BLOCK), st, s);
-            else SMC_LAUNCH((k_sm_on2<decltype(k)::value>), dim3((unsigned)M), dim3(SMC_BLOCK), st, s);
+            if (mcmc) SMC_LAUNCH((k_sm_mcmc<F_VAL(k)>), dim3((unsigned)((M + SMC_BLOCK - 1) / SMC_BLOCK)), dim3(SMC_BLOCK), st, s);
+            else SMC_LAUNCH((k_sm_on2<F_VAL(k)>), dim3((unsigned)M), dim3(SMC_BLOCK), st, s);
         });
     }
     return sm_download(f, island, M, idx, paths, idx_out_host, paths_out_host);
@@ -2246,13 +2255,10 @@ int smc_filter_csmc_paths(smc_filter* f, int backward, uint64_t seed, const doub
     const dim3 grid(1, f->a.n_islands);
     const int kform = f->plan.two_level ? 1 : 0, bw = backward ? 1 : 0;
     sm_with_kind(f->kind, [&](auto k) {
-        constexpr int KIND = decltype(k)::value;
-        if (f->a.N <= 256)
-            SMC_LAUNCH((k_csmc_path<KIND, 64>), grid, dim3(64), st, f->a, t, bw, kform, (u64)seed, (const double*)d_ulast,
-                       (const double*)d_u, idx, paths);
-        else
-            SMC_LAUNCH((k_csmc_path<KIND, SMC_BLOCK>), grid, dim3(SMC_BLOCK), st, f->a, t, bw, kform, (u64)seed,
+        f_with_small_block(f->a.N, [&](auto bs) {
+            SMC_LAUNCH((k_csmc_path<F_VAL(k), F_VAL(bs)>), grid, dim3(F_VAL(bs)), st, f->a, t, bw, kform, (u64)seed,
                        (const double*)d_ulast, (const double*)d_u, idx, paths);
+        });
     });
     SMC_LAUNCH_CHECK();
     if (idx_out_host) SMC_HIP_CHECK(hipMemcpyAsync(idx_out_host, idx, C * t * 8, hipMemcpyDeviceToHost, st));
@@ -2314,7 +2320,7 @@ int smc_filter_backward_reject(smc_filter* f, int island, int64_t M, int64_t max
         r.u_acc = d_uacc ? d_uacc + (size_t)b * per_step : nullptr;
         r.logC = d_logC + b;
         r.ctr = ctr + (size_t)b * SM_CTR_STRIDE;
-        sm_with_kind(f->kind, [&](auto k) { sm_launch_reject<decltype(k)::value>(st, s, r); });
+        sm_with_kind(f->kind, [&](auto k) { sm_launch_reject<F_VAL(k)>(st, s, r); });
     }
     std::vector<u64> counts(nb * SM_CTR_STRIDE);
     if (nb && (nprops_out_host || nexact_out_host))
@@ -2393,7 +2399,7 @@ static int os_paris_draw(smc_filter* f, SmPool& pool, SmArgs& s, OsParis& d)
     sm_cdf_of(f, s.lwt, s.rowt, s, tot, cdf);
     s.u = d_u; s.idx_next = targets; s.idx_out = d.idx;
     r.u_prop = d_uprop; r.u_acc = d_uacc; r.logC = d_logC; r.ctr = d.ctr;
-    sm_with_kind(f->kind, [&](auto k) { sm_launch_reject<decltype(k)::value>(st, s, r); });
+    sm_with_kind(f->kind, [&](auto k) { sm_launch_reject<F_VAL(k)>(st, s, r); });
     return SMC_OK;
 }
 // SMC_ONLINE_NAIVE, SMC_ONLINE_PARIS: Phi gathered along the ancestors, or the drawn indices (d.n_paris of them)
@@ -2548,7 +2554,7 @@ static int tf_items_pairs(smc_filter* f, int island, SmPool& pool, const SmArgs&
     q.Xi = w.Xi; q.u_f = d_uf; q.u_i = d_ui; q.J_in = J_in; q.I_in = I_in; q.mf = w.d_mf; q.mi = w.d_mi;
     q.items = w.items; q.Ni = Ni; q.P = P;
     sm_with_kind(f->kind, [&](auto k) {
-        SMC_LAUNCH((k_tf_pairs<decltype(k)::value>), dim3((unsigned)((P + SMC_BLOCK - 1) / SMC_BLOCK)), dim3(SMC_BLOCK), st, s, q, psi);
+        SMC_LAUNCH((k_tf_pairs<F_VAL(k)>), dim3((unsigned)((P + SMC_BLOCK - 1) / SMC_BLOCK)), dim3(SMC_BLOCK), st, s, q, psi);
     });
     return SMC_OK;
 }

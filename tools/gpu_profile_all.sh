@@ -5,6 +5,8 @@
 #   profiles/<tag>_<leg>_summary.txt   the table tools/summarise_prof.py prints
 #   profiles/traffic_<leg>.json        bench.py's roofline.traffic source (config + command inside)
 # are what to copy out of gpurun_out/<tag>/.
+# The first step that fails or runs into its time limit ends the run with that step's exit status: nothing more is
+# started on the device behind it.
 TAG=${1:-r12p}
 LEGS=${2:-"c2 c3_systematic c3_stratified c3_multinomial c4 c4_dense c4_collapsed c5 sqmc c2_strict c3_systematic_strict"}
 R=$GRAFT_REPO_ROOT
@@ -29,21 +31,24 @@ for leg in $LEGS; do
     sqmc)           ARGS="--workload c2 --qmc"; STEPS=40; CFG='{"workload":"c2","log2N":20,"islands":1,"scheme":"systematic","qmc":true}' ;;
     c2_strict)      ARGS="--workload c2 --strict"; STEPS=200; CFG='{"workload":"c2","log2N":20,"islands":1,"scheme":"systematic","strict":true}' ;;
     c3_systematic_strict) ARGS="--workload c3 --scheme systematic --strict"; CFG='{"workload":"c3","log2N":22,"islands":1,"scheme":"systematic","strict":true}' ;;
-    *) echo "unknown leg $leg"; continue ;;
+    *) echo "unknown leg $leg"; exit 2 ;;
   esac
   P=$O/prof_$leg
   mkdir -p $P
   CMD="python bench.py --full $ARGS --steps $STEPS --warmup 20 --reps 3 --no-cpu-baseline --no-other-workloads --no-profile"
   BENCH="python $R/bench.py --full $ARGS --steps $STEPS --warmup 20 --reps 3 --no-cpu-baseline --no-other-workloads --no-profile"
-  timeout 150 rocprofv3 --kernel-trace --stats -d $P/trace -o trace -- $BENCH > $P/trace.log 2>&1
+  timeout -k 10 150 rocprofv3 --kernel-trace --stats -d $P/trace -o trace -- $BENCH > $P/trace.log 2>&1 ||
+    { rc=$?; echo "=== $leg: the trace pass ended with status $rc"; tail -20 $P/trace.log; exit $rc; }
   IFS=';' read -ra PASSLIST <<< "$PASSES"
   for pass in "${PASSLIST[@]}"; do
     name=$(echo $pass | cut -d' ' -f1)
-    timeout 150 rocprofv3 --pmc $pass --kernel-trace -d $P/pmc_$name -o pmc -- $BENCH > $P/pmc_$name.log 2>&1
+    timeout -k 10 150 rocprofv3 --pmc $pass --kernel-trace -d $P/pmc_$name -o pmc -- $BENCH > $P/pmc_$name.log 2>&1 ||
+      { rc=$?; echo "=== $leg: the $name pass ended with status $rc"; tail -20 $P/pmc_$name.log; exit $rc; }
   done
   python $R/tools/summarise_prof.py $P --config "$CFG" --summary "${TAG}_${leg}_summary.txt" \
       --command "rocprofv3 --kernel-trace --stats -- $CMD ; rocprofv3 --pmc FETCH_SIZE (and, separately, WRITE_SIZE) --kernel-trace -- $CMD" \
-      > $O/${TAG}_${leg}_summary.txt 2>&1
+      > $O/${TAG}_${leg}_summary.txt 2>&1 ||
+    { rc=$?; echo "=== $leg: summarise_prof.py ended with status $rc"; tail -20 $O/${TAG}_${leg}_summary.txt; exit $rc; }
   cp $P/traffic.json $O/traffic_$leg.json 2>/dev/null
   grep -h '^{' $P/trace.log | tail -1 > $O/${TAG}_${leg}_bench_under_rocprof.json
   echo "=== $leg"; grep -v "^== traffic" $O/${TAG}_${leg}_summary.txt | grep -v "k_f_collect\|k_flush\|k_normal_rvs\|k_fill\|k_init" | head -40

@@ -545,6 +545,24 @@ int smc_filter_backward_reject(smc_filter* f, int island, int64_t M, int64_t max
                                const double* u_host,
                                int64_t* idx_out_host, double* paths_out_host,
                                int64_t* nprops_out_host, int64_t* nexact_out_host);
+/* SQMC filters (opts flag SMC_FLAG_SQMC) of the same kinds, keep_history == 1: M trajectories by QMC backward sampling
+ * (backward_sampling_qmc, smoothing.py:425-456) over the t steps executed so far.  The exact draw of SMC_BACKWARD_ON2 with
+ * two differences: u_host (M, t) row-major is ONE point set, row m the point of trajectory m (always the caller's: t is
+ * its dimension), and every lookup is made in the Hilbert order of its step's particles -- argsort(X_s), ties by index,
+ * -0.0 before +0.0, NaN last: idx[t-1, m] = h[first j with cdf(W_{t-1}[h])[j] > floor(u[m, t-1] Q)], and for s < t-1 the
+ * same search in the integer CDF of exp(l - max l), l_j = lw_s[h[j]] + log p_{s+1}(x_{s+1}^m | X_s[h[j]]).
+ * idx_out_host (t, M) int64 in particle numbering; paths_out_host (t, M) fp64 or NULL = X_s[idx[s]].
+ * geometry: 1 one workgroup per trajectory, 2 one thread per trajectory (workgroups of 256, the sorted particles staged
+ * through LDS), 0 picks by M; both return identical indices.  Per step one radix sort and one gather into a slab of 2 N
+ * words that the next step overwrites.  Reads the history only: the filter can go on stepping.  One synchronisation.
+ * SMC_ERR_INVALID: null arguments, a filter that is not SQMC ("QMC FFBS requires particles have been Hilbert ordered during
+ * the forward pass"), keep_history != 1, SVLEVERAGE, MVLINGAUSS, island out of range, M < 1, no step executed, geometry
+ * outside 0..2. */
+int smc_filter_backward_qmc(smc_filter* f, int island, int64_t M, int geometry, const double* u_host,
+                            int64_t* idx_out_host, double* paths_out_host);
+/* Measurements only: with enable != 0 every later smc_filter_backward_qmc call brackets its sort + gather launches with
+ * HIP events; last_sort_ms (or NULL) receives their summed time in the last such call. */
+int smc_debug_backward_qmc_timing(int enable, double* last_sort_ms);
 /* An additive function whose terms are polynomials of degree <= 2 in each argument, K <= 8 components:
  * psi_0(x) = sum_j c0[k][j] x^j at t = 0, psi_t(xp, x) = sum_ij c[k][i][j] xp^i x^j at t >= 1. */
 typedef struct smc_addfunc {

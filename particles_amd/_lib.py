@@ -175,6 +175,8 @@ SIGNATURES = {
                                            P(c_dbl), P(c_i64), P(c_dbl)]),
     "smc_filter_backward_reject": (c_int, [c_vp, c_int, c_i64, c_i64, c_u64, P(c_dbl), P(c_i64), P(c_dbl), P(c_dbl),
                                            P(c_dbl), P(c_dbl), P(c_i64), P(c_dbl), P(c_i64), P(c_i64)]),
+    "smc_filter_backward_qmc": (c_int, [c_vp, c_int, c_i64, c_int, P(c_dbl), P(c_i64), P(c_dbl)]),
+    "smc_debug_backward_qmc_timing": (c_int, [c_int, P(c_dbl)]),
     "smc_filter_online_smooth": (c_int, [c_vp, c_int, c_int, P(SmcAddFunc), c_vp, c_vp, c_vp, c_int, c_i64, c_u64, c_dbl,
                                          P(c_dbl), P(c_dbl), P(c_dbl), P(c_i64), P(c_i64), P(c_dbl)]),
     "smc_filter_two_filter": (c_int, [c_vp, c_int, c_vp, c_int, c_i64, c_int, P(SmcAddFunc), P(c_dbl), P(c_dbl), P(c_dbl),

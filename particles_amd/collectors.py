@@ -555,11 +555,72 @@ class RollingParticleHistory:
         return np.array(Bs)
 
 
+# (the reference's words, smoothing.py:271-276)
+_QMC_FFBS_ERR = "QMC FFBS requires particles have been Hilbert ordered during the forward pass"
+
+
+def _qmc_points(M, T, seed, replay):
+    """The (M, T) point set of ``backward_sampling_qmc``: ``replay["u"]``, else ``rqmc.sobol_points(M, T, seed)``."""
+    if M < 1:
+        raise ValueError("backward sampling: M must be at least 1")
+    if T < 1:
+        raise ValueError("backward sampling: no step has run yet")
+    replay = dict(replay or {})
+    unknown = set(replay) - {"u"}
+    if unknown:
+        raise ValueError("backward sampling: unknown replay tape(s) %s" % sorted(unknown))
+    if replay.get("u") is None:
+        from . import rqmc
+        return np.ascontiguousarray(rqmc.sobol_points(M, T, seed))
+    u = np.ascontiguousarray(replay["u"], dtype=np.float64)
+    if u.shape != (M, T):
+        raise ValueError("backward sampling: replay['u'] has shape %s, expected %s" % (u.shape, (M, T)))
+    return u
+
+
 class ParticleHistory(RollingParticleHistory):
     def __init__(self, fk, qmc):
         self.X, self.A, self.wgts = [], [], []
         self.fk = fk
         self.qmc = bool(qmc)
+        if qmc:
+            self.h_orders = []           # h_orders[t] = hilbert_sort(X_t), t < T - 1 (smoothing.py:247-254)
+
+    def save(self, smc):
+        RollingParticleHistory.save(self, smc)
+        if self.qmc and hasattr(smc, "h_order"):
+            self.h_orders.append(smc.h_order)
+
+    def backward_sampling_qmc(self, M, replay=None, seed=None, return_idx=False):
+        """QMC backward sampling (smoothing.py:425-456) on a history kept on the host: the NumPy route, the reference's
+        method line by line.  Returns its list of T arrays ``paths[t]`` of shape (M,); with ``return_idx`` also the (T, M)
+        int64 particle indices.
+
+        replay : ``{"u": (M, T)}`` supplies the points; otherwise ``rqmc.sobol_points(M, T, seed)``."""
+        if not hasattr(self, "h_orders"):
+            raise ValueError(_QMC_FFBS_ERR)
+        from . import hilbert
+        M, T = int(M), self.T
+        u = _qmc_points(M, T, seed, replay)
+        host = lambda a: np.asarray(a.get() if isinstance(a, _lib.DeviceArray) else a)
+        X = [host(x) for x in self.X]
+        hT = host(hilbert.hilbert_sort(X[-1])).astype(np.int64)
+        idx = np.empty((T, M), dtype=np.int64)
+        pos = np.searchsorted(np.cumsum(host(self.wgts[-1].W)[hT]), u[:, -1])
+        idx[-1] = hT[pos]
+        paths = [X[-1][hT][pos]]
+        for t in reversed(range(T - 1)):
+            h = host(self.h_orders[t]).astype(np.int64)
+            lw = host(self.wgts[t].lw)
+            pos = np.empty(M, dtype=np.int64)
+            for m, xn in enumerate(paths[-1]):
+                lwm = lw + host(self.fk.logpt(t + 1, X[t], np.full(X[t].shape, xn)))
+                cw = np.cumsum(_exp_and_normalise_cols(lwm[h]))      # use ordered version here
+                pos[m] = np.searchsorted(cw, u[m, t])
+            idx[t] = h[pos]
+            paths.append(X[t][h][pos])
+        paths.reverse()
+        return (paths, idx) if return_idx else paths
 
     def backward_sampling_ON2(self, M, **kw):
         """Backward sampling runs on the device-resident history of a fused filter
@@ -609,6 +670,13 @@ class _LazySteps:
         return (self[i] for i in range(len(self)))
 
 
+class _LazyOrders(_LazySteps):
+    """... over all steps but the last: the reference saves the order of X_t when step t + 1 resamples."""
+
+    def __len__(self):
+        return max(self._smc._n - 1, 0)
+
+
 class DeviceParticleHistory:
     """``ParticleHistory`` (smoothing.py:222-255: ``X``, ``A``, ``wgts`` of every
     step, ``compute_trajectories``) of a fused run: the history never leaves HBM
@@ -624,6 +692,9 @@ class DeviceParticleHistory:
         # hist.A[0] is the A of a filter that has not resampled yet: None (core.py:229)
         self.A = _LazySteps(smc, self._A_at)
         self.wgts = _LazySteps(smc, self._wgts_at)
+        if smc.qmc:
+            # h_orders[t] = hilbert_sort(X_t), t < T - 1 (smoothing.py:247-254), sorted on the device when read
+            self.h_orders = _LazyOrders(smc, self._h_order_at)
 
     def _X_at(self, t):
         return self._smc._history(_lib.FIELD_X, t)
@@ -749,6 +820,48 @@ class DeviceParticleHistory:
             max_trials = M
         max_trials = int(min(max_trials, _lib.REJECT_MAX_TRIALS))
         return self._backward(_lib.BACKWARD_REJECT, M, max_trials, seed, island, replay, return_idx)
+
+    _GEOMETRIES = {None: 0, "auto": 0, 0: 0, "workgroup": 1, 1: 1, "thread": 2, 2: 2}
+
+    def backward_sampling_qmc(self, M, seed=None, island=0, replay=None, return_idx=False, geometry=None):
+        """QMC backward sampling (smoothing.py:425-456) of an SQMC filter, on the device: exact FFBS whose M x T uniforms
+        are one randomised Sobol' point set and whose every inverse-CDF lookup is made in the Hilbert order of its
+        step's particles (smc_filter_backward_qmc; per step one radix sort and one gather, never T sorted copies).
+
+        Returns the reference's list of T arrays ``paths[t]`` of shape (M,) (not squeezed for M = 1, as the reference's
+        method does not); with ``return_idx`` also the (T, M) int64 particle indices.
+
+        seed : of ``rqmc.sobol_points(M, T, seed)``, the host-generated point set; None: a fresh one.
+        replay : ``{"u": (M, T)}`` supplies the points, row m the point of trajectory m.
+        geometry : None / "auto" picks by M; "workgroup" (1) one workgroup per trajectory, "thread" (2) one thread per
+            trajectory -- the same indices either way.
+        """
+        smc = self._smc
+        if not smc.qmc:
+            raise ValueError(_QMC_FFBS_ERR)
+        if geometry not in self._GEOMETRIES and not isinstance(geometry, int):
+            raise ValueError("backward sampling: unknown geometry %r" % (geometry,))
+        M, T = int(M), smc._n
+        u = _qmc_points(M, T, seed, replay)
+        idx = np.empty((T, M), dtype=np.int64)
+        paths = np.empty((T, M))
+        try:
+            _lib.check(_lib.lib().smc_filter_backward_qmc(
+                smc._f, int(island), M, int(self._GEOMETRIES.get(geometry, geometry)), u.ctypes.data_as(_lib.P(_lib.c_dbl)),
+                idx.ctypes.data_as(_lib.P(_lib.c_i64)), paths.ctypes.data_as(_lib.P(_lib.c_dbl))))
+        except ValueError as e:
+            if "model kind" in str(e):
+                raise NotImplementedError(str(e)) from None
+            raise
+        out = [paths[t].copy() for t in range(T)]
+        return (out, idx) if return_idx else out
+
+    def _h_order_at(self, t):
+        from . import hilbert
+        if t >= self._smc._n - 1:
+            raise IndexError("history index out of range")
+        h = hilbert.hilbert_sort(_lib.DeviceArray.from_numpy(self._smc._history(_lib.FIELD_X, t)))
+        return np.asarray(h.get() if isinstance(h, _lib.DeviceArray) else h, dtype=np.int64)
 
     def _two_filter_on_device(self, info, phi, loggamma):
         from .state_space_models import QuadAddFunc, QuadLogGamma

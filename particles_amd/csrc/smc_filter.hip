@@ -10,6 +10,7 @@
 #include "smc_filter_wide.h"
 #include "smc_filter_strict.h"
 #include "smc_smooth.h"
+#include "smc_smooth_qmc.h"
 #include "smc_online.h"
 #include "smc_twofilter.h"
 #include "smc_csmc.h"
@@ -2331,6 +2332,121 @@ int smc_filter_backward_reject(smc_filter* f, int island, int64_t M, int64_t max
         if (nexact_out_host) nexact_out_host[b] = (int64_t)counts[b * SM_CTR_STRIDE + SM_CTR_NEXACT];
     }
     return SMC_OK;
+}
+
+// Backward sampling for SQMC filters (smc_smooth_qmc.h): exact FFBS whose lookups are made in the sorted order of each
+// step's particles, with the caller's point set.  Per step: the sort, one gather into the one-step slab, one draw launch
+// in either geometry.  smc_debug_backward_qmc_timing: HIP events around the sort + gather launches of every step
+// (measurements only: tools/ffbs_qmc_perf.py).
+static const char* smq_check_filter(smc_filter* f, int island, const void* u_host, const void* idx_out_host)
+{
+    if (!(f && u_host && idx_out_host)) return "null argument";
+    if (!f->plan.sqmc()) return "QMC FFBS requires particles have been Hilbert ordered during the forward pass";
+    if (!(f->a.hist == 1)) return "the filter was created without a whole history (keep_history = 1)";
+    if (!(f->kind != SMC_MODEL_SVLEVERAGE)) return "model kind SVLEVERAGE is not supported: its transition reads y_{t-1}";
+    if (!(f->kind != SMC_MODEL_MVLINGAUSS)) return "model kind MVLINGAUSS is not supported: univariate models only";
+    if (!sm_kind_ok(f->kind)) return "model kind is not supported";
+    if (!(island >= 0 && island < f->a.n_islands)) return "island out of range";
+    return nullptr;
+}
+static bool g_smq_timing = false;
+static double g_smq_sort_ms = 0.0;
+int smc_debug_backward_qmc_timing(int enable, double* last_sort_ms)
+{
+    g_smq_timing = enable != 0;
+    if (last_sort_ms) *last_sort_ms = g_smq_sort_ms;
+    return SMC_OK;
+}
+struct SmqEvents {                     // one pair per sorted step, read after the call's synchronisation
+    std::vector<hipEvent_t> ev;
+    bool on;
+    explicit SmqEvents(bool enable) : on(enable) {}
+    ~SmqEvents() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+    void mark(hipStream_t st)
+    {
+        hipEvent_t e;
+        if (on && hipEventCreate(&e) == hipSuccess) { ev.push_back(e); (void)hipEventRecord(e, st); }
+    }
+    double total_ms() const
+    {
+        double ms = 0.0;
+        for (size_t i = 0; i + 1 < ev.size(); i += 2) {
+            float d = 0.f;
+            if (hipEventElapsedTime(&d, ev[i], ev[i + 1]) == hipSuccess) ms += d;
+        }
+        return ms;
+    }
+};
+
+int smc_filter_backward_qmc(smc_filter* f, int island, int64_t M, int geometry, const double* u_host,
+                            int64_t* idx_out_host, double* paths_out_host)
+{
+    sm_enter(f);
+    const char* bad = smq_check_filter(f, island, u_host, idx_out_host);
+    SMC_REQUIRE(!bad, bad);
+    SMC_REQUIRE(M >= 1 && M < ((int64_t)1 << 31), "M must be at least 1 (and below 2^31)");
+    SMC_REQUIRE(f->t_host >= 1, "no step has run yet");
+    SMC_REQUIRE(geometry >= 0 && geometry <= 2, "geometry must be 0 (auto), 1 (workgroup per trajectory) or 2 (thread per trajectory)");
+    const i64 t = f->t_host, N = f->a.N;
+    SMC_REQUIRE(N < ((i64)1 << 31), "N must stay below 2^31 (the radix sort)");
+    if (geometry == 0) geometry = M >= SMQ_THREAD_MIN_M ? 2 : 1;
+    hipStream_t st = f->ctx->stream;
+    SmPool pool(f->ctx);
+    const unsigned nch = (unsigned)((N + SM_CHUNK - 1) / SM_CHUNK);
+    const unsigned nblkN = (unsigned)((N + SMC_BLOCK - 1) / SMC_BLOCK), nblkM = (unsigned)((M + SMC_BLOCK - 1) / SMC_BLOCK);
+    i64* idx = nullptr;
+    u64 *cdf = nullptr, *tot = nullptr;
+    double *paths = nullptr, *d_u = nullptr, *d_ut = nullptr, *xs = nullptr, *ls = nullptr;
+    char* ws = nullptr;
+    pool.get((size_t)t * M, &idx);
+    pool.get((size_t)N, &cdf);
+    pool.get((size_t)nch, &tot);
+    pool.get((size_t)N, &xs);
+    pool.get((size_t)N, &ls);
+    pool.get(smc_rs_ws_bytes(N), &ws);
+    pool.get((size_t)t * M, &d_ut);
+    if (paths_out_host) pool.get((size_t)t * M, &paths);
+    pool.upload(u_host, (size_t)t * M, &d_u);
+    int rc = pool.status();
+    if (rc != SMC_OK) return rc;
+    SMC_HIP_CHECK(hipMemsetAsync(idx, 0, (size_t)t * M * 8, st));          // (every index a kernel reads is in range)
+    SMC_LAUNCH(k_smq_transpose, dim3((unsigned)(((size_t)t * M + SMC_BLOCK - 1) / SMC_BLOCK)), dim3(SMC_BLOCK), st,
+               (const double*)d_u, (i64)M, t, d_ut);
+
+    SmqEvents events(g_smq_timing);
+    SmArgs s = sm_args(f, island, M, 0, cdf);
+    for (i64 b = t - 1; b >= 0; --b) {
+        u64* order = nullptr;
+        events.mark(st);
+        if ((rc = smc_rs_sort_ws(f->ctx, sm_X(f, island, b), nullptr, N, 0, ws, nullptr, &order, b != t - 1)) != SMC_OK) {
+            smc_set_error("smc_filter_backward_qmc: the sort failed: %s", hipGetErrorString(hipGetLastError()));
+            return rc;
+        }
+        SMC_LAUNCH(k_smq_gather, dim3(nblkN), dim3(SMC_BLOCK), st, (const i64*)order, sm_X(f, island, b), sm_lw(f, island, b), N,
+                   xs, ls);
+        events.mark(st);
+        if (b == t - 1) {
+            s.t = (u32)b;
+            s.idx_out = idx + (size_t)b * M;
+        } else {
+            sm_step_args(f, island, b, idx, s);
+        }
+        s.Xt = xs; s.lwt = ls;                                                // the slab, and what its positions stand for
+        s.h = (const i64*)order;
+        s.u = d_ut + (size_t)b * M;
+        if (b == t - 1) {
+            sm_cdf_of(f, ls, sm_rows(f, island) + (size_t)b * SUMM_STRIDE, s, tot, cdf);
+            SMC_LAUNCH(k_smq_draw_last, dim3(nblkM), dim3(SMC_BLOCK), st, s);
+            continue;
+        }
+        sm_with_kind(f->kind, [&](auto k) {
+            if (geometry == 2) SMC_LAUNCH((k_smq_thread<F_VAL(k)>), dim3(nblkM), dim3(SMC_BLOCK), st, s);
+            else SMC_LAUNCH((k_smq_wg<F_VAL(k)>), dim3((unsigned)M), dim3(SMC_BLOCK), st, s);
+        });
+    }
+    rc = sm_download(f, island, M, idx, paths, idx_out_host, paths_out_host);
+    if (rc == SMC_OK && events.on) g_smq_sort_ms = events.total_ms();
+    return rc;
 }
 
 // On-line smoothing (smc_online.h): one update behind the step just run.  Stateless: Phi, X_{t-1} and lw_{t-1} are the

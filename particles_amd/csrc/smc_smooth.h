@@ -37,6 +37,8 @@ struct SmArgs {
     const i64* idx_next;        // (M) indices drawn for step t + 1
     i64* idx_out;               // (M) indices of step t
     const u64* cdf;             // (N) inclusive integer CDF of W_t (MCMC, last row)
+    const i64* h;               // null, or (N): Xt, lwt (and cdf) are a slab in sorted order whose position j holds
+                                // particle h[j] (smc_smooth_qmc.h); a draw finds a position and stores h[position]
     i64 N, M;
     u64 seed;
     u32 t, island;
@@ -107,11 +109,16 @@ struct SmTrans {
         lsc = log(sc);
         aux = (KIND == SMC_MODEL_GORDON && s.aux) ? smc_ldg(s.aux) : 0.0;
     }
-    __device__ __forceinline__ double logpt(double xp, double xn) const
+    __device__ __forceinline__ double loc(double xp) const { return m_trans_loc<KIND>(p, xp, aux); }
+    // ... with the location of the source already formed (k_smq_thread stages it once per tile)
+    __device__ __forceinline__ double logpt_at(double loc_p, double xn) const
     {
-        return m_norm_logpdf(xn, m_trans_loc<KIND>(p, xp, aux), sc, rsc, lsc);
+        return m_norm_logpdf(xn, loc_p, sc, rsc, lsc);
     }
+    __device__ __forceinline__ double logpt(double xp, double xn) const { return logpt_at(loc(xp), xn); }
 };
+// the particle a drawn position stands for
+__device__ __forceinline__ i64 sm_particle(const SmArgs& s, i64 pos) { return s.h ? smc_ldg(s.h + pos) : pos; }
 
 // ---------------------------------------------------------------------------
 // integer CDF of W_t: chunk totals, then every chunk scans itself behind the totals before it
@@ -203,7 +210,7 @@ __device__ __forceinline__ void sm_on2_draw(const SmArgs& s, const i64 m, double
     }
     mx = smc_block_max(mx, smd);
     if (!(mx > -INFINITY)) {
-        if (threadIdx.x == 0) s.idx_out[m] = N - 1;
+        if (threadIdx.x == 0) s.idx_out[m] = sm_particle(s, N - 1);
         return;
     }
     const i64 R = ((N + SMC_BLOCK - 1) / SMC_BLOCK) * 64;
@@ -244,7 +251,7 @@ __device__ __forceinline__ void sm_on2_draw(const SmArgs& s, const i64 m, double
         }
         const u64 inc = smc_wave_scan_add_u64(q);
         const u64 cum = run + inc;
-        if (cum > thr && cum - q <= thr) s.idx_out[m] = n;       // exactly one lane of the launch's workgroup
+        if (cum > thr && cum - q <= thr) s.idx_out[m] = sm_particle(s, n);   // exactly one lane of the launch's workgroup
         run += smc_readlane64(inc, 63);
         if (run > thr) break;
     }

@@ -32,6 +32,18 @@ def sobol(N, d):
     return out
 
 
+def sobol_points(M, T, seed=None):
+    """(M, T) scrambled Sobol' points in (0, 1) on the host, reproducible from ``seed``: the point set of
+    ``backward_sampling_qmc`` (smoothing.py:439 ``rqmc.sobol(M, self.T)``; T is the dimension, beyond the device
+    generator's 10).  ``seed=None``: a fresh one, derived like a filter's default seed."""
+    from scipy.stats import qmc
+    if seed is None:
+        from .core import _default_seed
+        seed = _default_seed()
+    seed = int(seed) & (2 ** 64 - 1)
+    return safe_generate(int(M), int(T), lambda d: qmc.Sobol(d, seed=seed))
+
+
 def sobol_sorted(N, d):
     """``u = sobol(N, d); u[np.argsort(u[:, 0])]`` -- the only way SQMC reads its points
     (core.py:343-347) -- or None when only the generic route exists.  With device-generated points

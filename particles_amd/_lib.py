@@ -319,6 +319,25 @@ def next_counter():
     return _counter
 
 
+_seed_counter = [0]
+
+
+def _default_seed():
+    """Philox key of a run created without ``seed``: a function of numpy's legacy generator
+    state (so ``numpy.random.seed`` makes runs repeatable) that does NOT advance it -- the
+    reference's ``SMC.__init__`` draws nothing, and a run replaying the reference's draws
+    must find the stream where the reference finds it."""
+    import zlib
+    st = np.random.get_state()
+    _seed_counter[0] += 1
+    return (zlib.crc32(st[1].tobytes()) ^ (int(st[2]) * 2654435761) ^ (_seed_counter[0] << 20)) & (2 ** 31 - 1)
+
+
+def u64_seed(seed):
+    """``seed`` as the C ABI's uint64 Philox key: a fresh ``_default_seed()`` if None, masked to 64 bits."""
+    return int(_default_seed() if seed is None else seed) & (2 ** 64 - 1)
+
+
 def _device_array_from_host(a):
     return DeviceArray.from_numpy(a, dtype=a.dtype)
 
@@ -629,6 +648,11 @@ def as_device(a, dtype=None):
 
 def dptr(a):
     return a.ptr if a is not None else None
+
+
+def hptr(a, ct):
+    """A C-contiguous NumPy array as the ``POINTER(ct)`` argument of a host-pointer parameter; None stays None (NULL)."""
+    return a.ctypes.data_as(P(ct)) if a is not None else None
 
 
 def host_dbl(a):

@@ -24,7 +24,8 @@ from . import collectors
 from . import hilbert
 from . import resampling as rs
 from . import rqmc
-from ._lib import DeviceArray, check, lib
+from . import smoothing
+from ._lib import DeviceArray, _default_seed, check, lib  # noqa: F401 (rqmc and mcmc name core._default_seed)
 
 
 class FeynmanKac:
@@ -102,20 +103,6 @@ class _DeviceWeights:
         return self._smc.N
 
 
-_seed_counter = [0]
-
-
-def _default_seed():
-    """Philox key of a run created without ``seed``: a function of numpy's legacy generator
-    state (so ``numpy.random.seed`` makes runs repeatable) that does NOT advance it -- the
-    reference's ``SMC.__init__`` draws nothing, and a run replaying the reference's draws
-    must find the stream where the reference finds it."""
-    import zlib
-    st = np.random.get_state()
-    _seed_counter[0] += 1
-    return (zlib.crc32(st[1].tobytes()) ^ (int(st[2]) * 2654435761) ^ (_seed_counter[0] << 20)) & (2 ** 31 - 1)
-
-
 class SMC:
     """Particle filter / SMC algorithm (core.py:200-409), device-resident.
 
@@ -171,7 +158,7 @@ class SMC:
             self._user_collectors and all(isinstance(c, collectors.Moments) and c.mom_func is None
                                           for c in collect)
             and type(fk).default_moments is FeynmanKac.default_moments)
-        self.hist = collectors.generate_hist_obj(store_history, self)
+        self.hist = smoothing.generate_hist_obj(store_history, self)
         self._store_history = store_history
         if seed is None:
             seed = _default_seed()
@@ -201,9 +188,9 @@ class SMC:
             self._keep_history = int(store_history) if rolling else (1 if store_history is True else 0)
             self._create_filter(model, replay, use_graph, island_offset)
             if store_history is True:
-                self.hist = collectors.DeviceParticleHistory(self)
+                self.hist = smoothing.DeviceParticleHistory(self)
             elif rolling:       # RollingParticleHistory on the device: a ring of k slots
-                self.hist = collectors.DeviceRollingParticleHistory(self, store_history)
+                self.hist = smoothing.DeviceRollingParticleHistory(self, store_history)
         else:
             if n_islands != 1:
                 raise ValueError("n_islands > 1 needs a model of the fused family")
@@ -756,7 +743,7 @@ class SMC:
             self.step_async((T if nxt is None else nxt + 1) - self.t)
             if nxt is not None:
                 self.hist.X[nxt] = self.X
-                self.hist.wgts[nxt] = collectors._frozen_weights(self.wgts)
+                self.hist.wgts[nxt] = smoothing._frozen_weights(self.wgts)
         self.sync()
         if self.summaries and self.t > first:
             s = self._summ()[0]
@@ -770,7 +757,7 @@ class SMC:
     def run(self):
         """Run until completion (core.py:391-409); sets ``cpu_time``."""
         t0 = time.perf_counter()
-        partial = (self._fused and isinstance(self.hist, collectors.PartialParticleHistory)
+        partial = (self._fused and isinstance(self.hist, smoothing.PartialParticleHistory)
                    and not self.verbose and not (self._user_collectors and not self._device_moments))
         if partial:
             self._run_to_save_times()

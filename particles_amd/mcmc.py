@@ -11,11 +11,10 @@ chains is two launches.  Every other model runs the reference's two overrides on
 import numpy as np
 
 from . import _lib
-from .core import SMC, _default_seed
+from . import smoothing
+from .core import SMC
 from ._lib import DeviceArray, check, lib
 
-_DEVICE_KINDS = (_lib.MODEL_LINGAUSS, _lib.MODEL_STOCHVOL, _lib.MODEL_GORDON, _lib.MODEL_THETALOGISTIC,
-                 _lib.MODEL_DISCRETECOX)
 _MAX_N = 1024
 
 
@@ -23,10 +22,10 @@ def device_conditional(fk, N):
     """Does ``CSMC(fk, N)`` run conditional on the device (what ``smc_filter_set_conditional`` accepts)?"""
     fks = list(fk) if isinstance(fk, (list, tuple)) else [fk]
     for g in fks:
-        if g is None or getattr(g, "_fk_kind", None) != _lib.FK_BOOTSTRAP or not hasattr(g, "_device_model"):
+        if g is None or getattr(g, "_fk_kind", None) != _lib.FK_BOOTSTRAP:
             return False
-        model = g._device_model()
-        if model is None or model.get("params") is None or model["kind"] not in _DEVICE_KINDS:
+        model = smoothing.device_model(g)
+        if model is None or model.get("params") is None:
             return False
     return (1 <= N <= _MAX_N and not (_lib.path_flags() & _lib.PATH_FLAGS["SMC_NO_SMALL"])
             and SMC._will_fuse(fks[0], False, "multinomial", N=N))
@@ -115,27 +114,16 @@ def new_paths(pf, backward_step=False, seed=None, replay=None, return_idx=False)
     if not getattr(pf, "_fused", False) or getattr(pf, "_keep_history", 0) != 1:
         return _new_paths_host(pf, backward_step, return_idx)
     C, T = pf.n_islands, pf._n
-    replay = dict(replay or {})
-    unknown = set(replay) - {"u_last", "u"}
-    if unknown:
-        raise ValueError("new_paths: unknown replay tape(s) %s" % sorted(unknown))
-    tapes = {}
-    for k, shp in (("u_last", (C,)), ("u", (max(T - 1, 0), C))):
-        a = replay.get(k)
-        if a is not None:
-            a = np.ascontiguousarray(a, dtype=np.float64)
-            if a.shape != shp:
-                raise ValueError("new_paths: replay[%r] has shape %s, expected %s" % (k, a.shape, shp))
-        tapes[k] = a
-    if seed is None:
-        seed = _default_seed()
-    ptr = lambda a, ct: a.ctypes.data_as(_lib.P(ct)) if a is not None else None
+    tapes = smoothing.read_tapes("new_paths", replay, {"u_last": ((C,), np.float64),
+                                                       "u": ((max(T - 1, 0), C), np.float64)})
+    seed = _lib.u64_seed(seed)
+    ptr = _lib.hptr
     idx = np.empty((C, T), dtype=np.int64) if return_idx else None
     paths = np.empty((C, T))
     if T < 1:
         raise ValueError("new_paths: no step has run yet")
     dev = DeviceArray((C, T))
-    check(lib().smc_filter_csmc_paths(pf._f, 1 if backward_step else 0, int(seed) & (2 ** 64 - 1),
+    check(lib().smc_filter_csmc_paths(pf._f, 1 if backward_step else 0, seed,
                                       ptr(tapes["u_last"], _lib.c_dbl), ptr(tapes["u"], _lib.c_dbl),
                                       ptr(idx, _lib.c_i64), ptr(paths, _lib.c_dbl), dev.ptr))
     pf.paths_device = dev
